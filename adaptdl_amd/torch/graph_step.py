@@ -94,7 +94,17 @@ class HipGraphBackend(object):
 
     def __init__(self):
         self._pool = torch.cuda.graph_pool_handle()
-        self._side = torch.cuda.Stream()
+        # Warmup and capture share ONE stream.  When the caller already
+        # trains on a non-default stream that stream is used, so the
+        # parameters' AccumulateGrad nodes (which remember the stream
+        # they were created on) run on the capture stream too.  A node
+        # bound to the default stream instead pulls that stream into the
+        # capture as a parallel branch: the weight-gradient buffers were
+        # then consumed unordered against their reuse, and replays
+        # produced non-finite gradients.
+        cur = torch.cuda.current_stream()
+        self._side = cur if cur != torch.cuda.default_stream() \
+            else torch.cuda.Stream()
 
     def begin_generation(self):
         """Start a fresh capture generation (after graphs were dropped).
@@ -114,6 +124,9 @@ class HipGraphBackend(object):
     def warmup(self):
         """Eager warmup on a side stream (the torch.cuda.graph protocol:
         lazy inits must not land on the capture stream)."""
+        if torch.cuda.current_stream() == self._side:
+            yield
+            return
         self._side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(self._side):
             yield
@@ -121,7 +134,7 @@ class HipGraphBackend(object):
 
     def capture(self, fn):
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, pool=self._pool):
+        with torch.cuda.graph(graph, pool=self._pool, stream=self._side):
             out = fn()
         return graph, out
 

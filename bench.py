@@ -24,6 +24,13 @@ Protocol (driver contract):
 warmup optimizer steps feed the performance-model fit, the goodput model
 then picks (atomic_bsz, accum_steps), and EXACTLY K optimizer steps are
 timed between barrier+synchronize brackets.  Rank 0 prints one JSON line.
+--dump-outputs DIR additionally runs, after the timed steps, one more
+optimizer step of the timed path from the seeded initial state and writes
+its loss and the model state it produced as DIR/<name>.npy, for
+output-for-output comparison of two builds (weights, sample pool and data
+order are seeded, so that step's inputs are the same in every run).
+--full is reserved for measurements beyond the headline figure; a plain
+run does only what the result line needs.
 
 Metric stability: the statistical-efficiency factor is computed from a
 fixed-seed gradient-statistics probe run at the *initial* weights with
@@ -331,6 +338,58 @@ WORKLOADS = {cls.name: cls for cls in
               BertBase, BertMini)}
 
 
+# --dump-outputs budget: 64 MB in all, split between the two state files
+# (loss.npy is 4 bytes).  Larger states are sampled at fixed seeded indices.
+DUMP_MAX_ELEMS = {"params": 12 * 2 ** 20, "buffers": 2 * 2 ** 20}
+DUMP_SAMPLE_SEED = 20240
+
+
+def _flat_sample(tensors, max_elems):
+    """Concatenate ``tensors`` (flattened, fp32, on CPU) into one vector;
+    above ``max_elems`` keep a fixed seeded sample in index order, so two
+    runs with the same arguments pick the same elements."""
+    if not tensors:
+        return torch.zeros(0)
+    flat = torch.cat([t.detach().reshape(-1).float().cpu() for t in tensors])
+    if flat.numel() > max_elems:
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(0, flat.numel(), (max_elems,), generator=g)
+        flat = flat[idx.sort().values]
+    return flat
+
+
+def _state_tensors(model):
+    """Every parameter and buffer of ``model`` (the training state that
+    --dump-outputs rewinds to its seeded initial value)."""
+    return [p for _, p in model.named_parameters()] + \
+        [b for _, b in model.named_buffers()]
+
+
+def dump_outputs(out_dir, loss, model):
+    """Write what the dump step (one more optimizer step of the timed
+    path, run from the seeded initial state) handed back to its caller:
+    the step's loss (of its final microbatch) and the model state the
+    optimizer step left behind, as float32 .npy files.
+
+      loss.npy     shape (1,)
+      params.npy   all parameters, named_parameters() order, flattened
+      buffers.npy  floating-point buffers (BN running statistics)
+    """
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {
+        "loss": loss.detach().reshape(1).float().cpu(),
+        "params": _flat_sample([p for _, p in model.named_parameters()],
+                               DUMP_MAX_ELEMS["params"]),
+        "buffers": _flat_sample([b for _, b in model.named_buffers()
+                                 if b.is_floating_point()],
+                                DUMP_MAX_ELEMS["buffers"]),
+    }
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.numpy().astype(np.float32, copy=False))
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--model", choices=sorted(WORKLOADS),
@@ -352,6 +411,16 @@ def main():
                         default="channels_last",
                         help="channels_last keeps MIOpen on its native NHWC "
                              "igemm kernels with no transpose kernels")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, run one more step "
+                             "of the timed path from the seeded initial "
+                             "state and write its loss and the resulting "
+                             "model state to DIR/<name>.npy (float32)")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the measurements beyond the "
+                             "headline figure (there are none yet: the "
+                             "plain run already does only what its "
+                             "result line needs)")
     args = parser.parse_args()
     args.warmup = max(args.warmup, 5)
 
@@ -379,8 +448,41 @@ def main():
     device = torch.device("cuda", torch.cuda.current_device()) if use_gpu \
         else torch.device("cpu")
 
+    if use_gpu:
+        # Train on one non-default stream from the start: the graph
+        # stepper captures on the caller's stream, and the parameters'
+        # AccumulateGrad nodes must have been created on that stream.
+        torch.cuda.set_stream(torch.cuda.Stream())
+
     workload = wl_cls(args, device, use_gpu)
     adp, optim, loader = workload.build()
+
+    # --dump-outputs: the state a training step consumes (weights, BN
+    # statistics, momentum, GNS averages) drifts chaotically over the
+    # warmup and timed steps (atomics-order rounding, amplified by every
+    # update), so the last timed step's inputs are not the same from run
+    # to run.  Snapshot the seeded initial state here; after the timed
+    # steps it is restored and ONE more optimizer step of the timed path
+    # (same graphs, same batch configuration, the loader's next batches)
+    # runs from it.  That step's outputs are what is written.
+    import copy
+    init_state = None
+    gns_init = None
+    if args.dump_outputs:
+        with torch.no_grad():
+            init_state = [t.detach().clone()
+                          for t in _state_tensors(adp.module)]
+        gns_init = copy.deepcopy(dict(optim.state["gns"]))
+
+    def rewind_to_init():
+        with torch.no_grad():
+            for t, saved in zip(_state_tensors(adp.module), init_state):
+                t.copy_(saved)
+        optim.state["gns"].clear()
+        optim.state["gns"].update(copy.deepcopy(gns_init))
+        adp.gns._prev_total_sqr = None
+        if hasattr(optim, "reset_state"):
+            optim.reset_state()
 
     # Fixed-seed gradient-statistics probe at the initial weights: run
     # the first few optimizer cycles with lr=0 (weights never move) and
@@ -401,18 +503,24 @@ def main():
         # training trajectory (and the goodput model's own batch-size
         # choice) untouched — the probe only produces the deterministic
         # grad params used for the final efficiency quote.
-        import copy
         gns_backup = copy.deepcopy(dict(optim.state["gns"]))
 
     graph_stepper = None  # ADAPTDL_HIPGRAPH=1: set before the probe pass
+    last_loss = None  # --dump-outputs: newest microbatch's loss value
 
     def train_step(batch):
+        nonlocal last_loss
         batch = workload.prep(batch)  # H2D etc., outside any capture
         parts = batch if isinstance(batch, (tuple, list)) else (batch,)
         if graph_stepper is not None:
-            graph_stepper.microbatch(*parts)
+            loss = graph_stepper.microbatch(*parts)
         else:
-            workload.fwd_bwd(*parts)
+            loss = workload.fwd_bwd(*parts)
+        if args.dump_outputs and loss is not None:
+            # Detached alias of the loss storage (no kernel, no host
+            # sync); the autograd graph is released as in a plain run.
+            last_loss = loss.detach()
+        del loss
         optim.step()
 
     def barrier_sync():
@@ -426,6 +534,7 @@ def main():
     timed_steps = 0
     t0 = None
     elapsed = None
+    end_grad_params = None
     global_batch = None
 
     for _epoch in adl.remaining_epochs_until(10 ** 6):
@@ -471,7 +580,16 @@ def main():
                     if timed_steps >= args.steps:
                         barrier_sync()
                         elapsed = time.time() - t0
-                        phase = "done"
+                        end_grad_params = \
+                            _metrics._metrics_state().grad_params
+                        if init_state is not None:
+                            rewind_to_init()
+                            phase = "dump"
+                        else:
+                            phase = "done"
+                elif phase == "dump":
+                    # The untimed dump step just completed.
+                    phase = "done"
                 if restart_pass or phase == "done":
                     break
             if restart_pass:
@@ -523,13 +641,16 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_loss, adp.module)
+
     if rank == 0:
         atomic_bsz = loader._elastic.current_local_bsz
         accum = loader._elastic.accumulation_steps
         samples_per_sec = args.steps * global_batch / elapsed
         grad_params = probe_grad_params
         if grad_params is None:
-            grad_params = _metrics._metrics_state().grad_params
+            grad_params = end_grad_params
         if grad_params is not None:
             efficiency = float(GoodputFunction(
                 (1.0,) * 7, grad_params,

@@ -102,6 +102,85 @@ def test_bench_stat_efficiency_is_deterministic(tmp_path):
     assert r1["config"]["stat_efficiency_source"] == "fixed-seed-init-probe"
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the dump step's loss and model state as
+    float32 .npy files within the 64 MB budget; --full is accepted and
+    leaves the result line's contract intact."""
+    import numpy as np
+    out_dir = tmp_path / "dump"
+    r = _run_bench(tmp_path / "ckpt",
+                   ["--steps", "2", "--warmup", "5", "--max-batch", "256",
+                    "--dataset-size", "1024", "--pool", "128", "--full",
+                    "--dump-outputs", str(out_dir)])
+    assert r["steps"] == 2
+    assert r["ms_per_step"] > 0
+    files = sorted(os.listdir(out_dir))
+    assert files == ["buffers.npy", "loss.npy", "params.npy"]
+    arrays = {f[:-4]: np.load(out_dir / f) for f in files}
+    assert sum(a.nbytes for a in arrays.values()) <= 64e6
+    for name, a in arrays.items():
+        assert a.dtype == np.float32, name
+        assert a.ndim == 1 and a.size > 0, name
+        assert np.isfinite(a).all(), name
+    assert arrays["loss"].shape == (1,)
+    from adaptdl_amd.models import ResNet18
+    model = ResNet18()
+    assert arrays["params"].size == \
+        sum(p.numel() for p in model.parameters())
+    assert arrays["buffers"].size == \
+        sum(b.numel() for b in model.buffers() if b.is_floating_point())
+
+
+def test_bench_dump_outputs_repeat(tmp_path):
+    """Two runs with the same arguments dump the same outputs: the dump
+    step starts from the seeded initial state, so only fp32 summation
+    order may differ (fixed batch size here: the adaptive choice depends
+    on measured CPU step times).  One SGD step of fp32 math: 1e-5
+    relative is ~100 ulp, far below any real difference in the path."""
+    import numpy as np
+    args = ["--steps", "2", "--warmup", "5", "--init-batch", "64",
+            "--max-batch", "0", "--dataset-size", "1024", "--pool", "64"]
+    dumps = []
+    for tag in ("a", "b"):
+        out_dir = tmp_path / ("dump_" + tag)
+        _run_bench(tmp_path / ("ckpt_" + tag),
+                   args + ["--dump-outputs", str(out_dir)])
+        dumps.append({f: np.load(out_dir / f)
+                      for f in sorted(os.listdir(out_dir))})
+    assert sorted(dumps[0]) == ["buffers.npy", "loss.npy", "params.npy"]
+    for name in dumps[0]:
+        np.testing.assert_allclose(dumps[0][name], dumps[1][name],
+                                   rtol=1e-5, atol=1e-6, err_msg=name)
+    # The dump step really trained: parameters moved off the seeded init.
+    import torch
+    from adaptdl_amd.models import ResNet18
+    torch.manual_seed(1234)
+    init = torch.cat([p.detach().reshape(-1)
+                      for p in ResNet18().parameters()]).numpy()
+    assert not np.allclose(dumps[0]["params.npy"], init, rtol=0, atol=1e-6)
+    # ... by one step only: far closer to init than to zero.
+    assert np.abs(dumps[0]["params.npy"] - init).max() < 1.0
+
+
+def test_bench_dump_sample_is_fixed():
+    """Above the budget the dump keeps the same seeded elements every
+    time, in index order, so two builds' dumps line up."""
+    import torch
+    sys.path.insert(0, REPO)
+    try:
+        import bench
+    finally:
+        sys.path.remove(REPO)
+    parts = [torch.arange(0, 700.0).reshape(7, 100),
+             torch.arange(700.0, 1000.0)]
+    whole = bench._flat_sample(parts, 1000)
+    assert torch.equal(whole, torch.arange(0, 1000.0))
+    a = bench._flat_sample(parts, 64)
+    b = bench._flat_sample(parts, 64)
+    assert a.numel() == 64 and torch.equal(a, b)
+    assert torch.equal(a, a.sort().values)  # values == indices here
+
+
 def test_bench_model_bert(tmp_path):
     """BERT bench config (BASELINE configs[3] shape): FusedAdam +
     AdamScale + accumulation through the same JSON contract."""
