@@ -1,8 +1,8 @@
-// Python bindings for the adaptdl_amd CDNA4 kernels (gns_kernels.hip).
+// Python bindings for the adaptdl_amd CDNA4 kernels.
 // Launches on the current torch HIP stream so ordering with autograd-
 // produced gradients and RCCL all-reduces is inherited from stream order.
-// Kernel launches live in gns_kernels.hip (hipcc-compiled); this file is
-// host-only glue.
+// Kernel launches live in the hipcc-compiled .hip files; this file is
+// host-only glue and sees them through kernels.h alone.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -10,82 +10,7 @@
 
 #include <cmath>
 
-extern "C" {
-void launch_sqsum(const float*, long, double*, hipStream_t);
-void launch_scale_sqsum(float*, long, float, double*, hipStream_t);
-void launch_sqsum_diff_update(const float*, float*, long, double*,
-                              hipStream_t);
-void launch_sqsum_avg(const float*, const float*, long, double*,
-                      hipStream_t);
-void launch_precond_sqsum(const float*, const float*, long, float, float,
-                          double*, hipStream_t);
-void launch_precond_sqsum_dev(const float*, const float*, long,
-                              const float*, double*, hipStream_t);
-void launch_sqsum_bf16(const unsigned short*, long, double*, hipStream_t);
-void launch_scale_sqsum_bf16(unsigned short*, long, float, double*,
-                             hipStream_t);
-void launch_sqsum_diff_update_bf16(const unsigned short*, unsigned short*,
-                                   long, double*, hipStream_t);
-void launch_sqsum_avg_bf16(const unsigned short*, const unsigned short*,
-                           long, double*, hipStream_t);
-void launch_sqsum_fp16(const unsigned short*, long, double*, hipStream_t);
-void launch_scale_sqsum_fp16(unsigned short*, long, float, double*,
-                             hipStream_t);
-void launch_sqsum_diff_update_fp16(const unsigned short*, unsigned short*,
-                                   long, double*, hipStream_t);
-void launch_sqsum_avg_fp16(const unsigned short*, const unsigned short*,
-                           long, double*, hipStream_t);
-void launch_fused_sgd(float*, const float*, float*, long, float, float,
-                      float, float, int, int, hipStream_t);
-void launch_fused_adamw(float*, const float*, float*, float*, long, float,
-                        float, float, float, float, float, float, int,
-                        hipStream_t);
-void launch_bn_fwd(const unsigned short*, const unsigned short*,
-                   unsigned short*, long, int, const float*, const float*,
-                   float*, float*, float, float, int, int, float*, float*,
-                   float*, float*, float*, float*, hipStream_t);
-void launch_bn_bwd(const unsigned short*, const unsigned short*,
-                   const unsigned short*, unsigned short*, unsigned short*,
-                   long, int, const float*, const float*, const float*,
-                   const float*, const float*, int, int, float*, float*,
-                   float*, float*, float*, hipStream_t);
-int conv3x3_wrw_supported(int, int, int, int);
-int conv3x3_mm_supported(int, int, int, int);
-int conv3x3_s2_bwd_supported(int, int, int, int);
-int conv3x3_s2_fwd_supported(int, int, int, int);
-int conv3x3_s2_wrw_supported(int, int, int, int);
-int conv3x3_s2_bwd_w8b_supported(int, int, int, int);
-void launch_conv3x3_s2_bwd_w8b(const unsigned short*,
-                               const unsigned short*, unsigned short*,
-                               int, int, int, int, hipStream_t);
-int conv3x3_s2_wrw_nsplit(int, int, int, int, int);
-void launch_conv3x3_s2_wrw(const unsigned short*, const unsigned short*,
-                           float*, float*, int, int, int, int, int,
-                           hipStream_t);
-void launch_conv3x3_s2_fwd(const unsigned short*, const unsigned short*,
-                           unsigned short*, int, int, int, int, int,
-                           hipStream_t);
-void launch_conv3x3_s2_bwd(const unsigned short*, const unsigned short*,
-                           unsigned short*, int, int, int, int, int,
-                           hipStream_t);
-void launch_conv3x3_mm(const unsigned short*, const unsigned short*,
-                       unsigned short*, int, int, int, int, int,
-                       hipStream_t);
-int conv3x3_wrw_nsplit(int, int, int, int, int);
-void launch_conv3x3_wrw(const unsigned short*, const unsigned short*,
-                        float*, float*, int, int, int, int, int,
-                        hipStream_t);
-}
-
-// Mirror of the kernel-side stage-1 grid sizing (bn_kernels.hip).
-static long bn_num_rblocks(long m, long c) {
-    long rpb = 256 / (c / 8);
-    if (rpb < 1) rpb = 1;
-    long nb = (m + rpb - 1) / rpb;
-    if (nb > 1024) nb = 1024;
-    if (nb < 1) nb = 1;
-    return nb;
-}
+#include "kernels.h"
 
 namespace {
 
@@ -106,99 +31,63 @@ hipStream_t stream() {
 
 // The statistics entry points accept float32 (master-grad training)
 // plus bfloat16/float16 (true-low-precision-parameter models) buckets.
-bool is_bf16(const torch::Tensor& t) {
-    return t.scalar_type() == torch::kBFloat16;
+StatDtype stat_dtype(const torch::Tensor& t, const char* name) {
+    switch (t.scalar_type()) {
+    case torch::kFloat32: return STAT_F32;
+    case torch::kBFloat16: return STAT_BF16;
+    case torch::kHalf: return STAT_FP16;
+    default:
+        TORCH_CHECK(false, name, " must be float32, bfloat16, or float16");
+    }
 }
 
-bool is_fp16(const torch::Tensor& t) {
-    return t.scalar_type() == torch::kHalf;
-}
-
-void check_stat_in(const torch::Tensor& t, const char* name) {
+StatDtype check_stat_in(const torch::Tensor& t, const char* name) {
     TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
-    TORCH_CHECK(t.scalar_type() == torch::kFloat32 ||
-                t.scalar_type() == torch::kBFloat16 ||
-                t.scalar_type() == torch::kHalf,
-                name, " must be float32, bfloat16, or float16");
+    const StatDtype dtype = stat_dtype(t, name);
     TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
-}
-
-unsigned short* bf16_ptr(torch::Tensor& t) {
-    return reinterpret_cast<unsigned short*>(t.data_ptr<at::BFloat16>());
-}
-
-unsigned short* fp16_ptr(torch::Tensor& t) {
-    return reinterpret_cast<unsigned short*>(t.data_ptr<at::Half>());
+    return dtype;
 }
 
 void sqsum(torch::Tensor x, torch::Tensor out) {
-    check_stat_in(x, "x"); check_out(out);
+    const StatDtype dtype = check_stat_in(x, "x"); check_out(out);
     long n = x.numel();
     if (n == 0) return;
-    if (is_bf16(x))
-        launch_sqsum_bf16(bf16_ptr(x), n, out.data_ptr<double>(),
-                          stream());
-    else if (is_fp16(x))
-        launch_sqsum_fp16(fp16_ptr(x), n, out.data_ptr<double>(),
-                          stream());
-    else
-        launch_sqsum(x.data_ptr<float>(), n, out.data_ptr<double>(),
-                     stream());
+    launch_sqsum(dtype, x.data_ptr(), n, out.data_ptr<double>(), stream());
 }
 
 void scale_and_sqsum(torch::Tensor x, double scale, torch::Tensor out) {
-    check_stat_in(x, "x"); check_out(out);
+    const StatDtype dtype = check_stat_in(x, "x"); check_out(out);
     long n = x.numel();
     if (n == 0) return;
-    if (is_bf16(x))
-        launch_scale_sqsum_bf16(bf16_ptr(x), n, (float)scale,
-                                out.data_ptr<double>(), stream());
-    else if (is_fp16(x))
-        launch_scale_sqsum_fp16(fp16_ptr(x), n, (float)scale,
-                                out.data_ptr<double>(), stream());
-    else
-        launch_scale_sqsum(x.data_ptr<float>(), n, (float)scale,
-                           out.data_ptr<double>(), stream());
+    launch_scale_sqsum(dtype, x.data_ptr(), n, (float)scale,
+                       out.data_ptr<double>(), stream());
 }
 
 void sqsum_diff_update(torch::Tensor cur, torch::Tensor prev,
                        torch::Tensor out) {
-    check_stat_in(cur, "cur"); check_stat_in(prev, "prev");
+    const StatDtype dtype = check_stat_in(cur, "cur");
+    check_stat_in(prev, "prev");
     check_out(out);
     TORCH_CHECK(cur.numel() == prev.numel(), "cur/prev size mismatch");
     TORCH_CHECK(cur.scalar_type() == prev.scalar_type(),
                 "cur/prev dtype mismatch");
     long n = cur.numel();
     if (n == 0) return;
-    if (is_bf16(cur))
-        launch_sqsum_diff_update_bf16(bf16_ptr(cur), bf16_ptr(prev), n,
-                                      out.data_ptr<double>(), stream());
-    else if (is_fp16(cur))
-        launch_sqsum_diff_update_fp16(fp16_ptr(cur), fp16_ptr(prev), n,
-                                      out.data_ptr<double>(), stream());
-    else
-        launch_sqsum_diff_update(cur.data_ptr<float>(),
-                                 prev.data_ptr<float>(), n,
-                                 out.data_ptr<double>(), stream());
+    launch_sqsum_diff_update(dtype, cur.data_ptr(), prev.data_ptr(), n,
+                             out.data_ptr<double>(), stream());
 }
 
 void sqsum_avg(torch::Tensor cur, torch::Tensor prev, torch::Tensor out) {
-    check_stat_in(cur, "cur"); check_stat_in(prev, "prev");
+    const StatDtype dtype = check_stat_in(cur, "cur");
+    check_stat_in(prev, "prev");
     check_out(out);
     TORCH_CHECK(cur.numel() == prev.numel(), "cur/prev size mismatch");
     TORCH_CHECK(cur.scalar_type() == prev.scalar_type(),
                 "cur/prev dtype mismatch");
     long n = cur.numel();
     if (n == 0) return;
-    if (is_bf16(cur))
-        launch_sqsum_avg_bf16(bf16_ptr(cur), bf16_ptr(prev), n,
-                              out.data_ptr<double>(), stream());
-    else if (is_fp16(cur))
-        launch_sqsum_avg_fp16(fp16_ptr(cur), fp16_ptr(prev), n,
-                              out.data_ptr<double>(), stream());
-    else
-        launch_sqsum_avg(cur.data_ptr<float>(), prev.data_ptr<float>(), n,
-                         out.data_ptr<double>(), stream());
+    launch_sqsum_avg(dtype, cur.data_ptr(), prev.data_ptr(), n,
+                     out.data_ptr<double>(), stream());
 }
 
 void precond_sqsum(torch::Tensor g, torch::Tensor v, double beta2,
@@ -280,6 +169,14 @@ void check_vecf(const torch::Tensor& t, long n, const char* name) {
                 name, " must be a contiguous fp32 GPU tensor of size ", n);
 }
 
+// Python-visible bn_num_rblocks: callers size ws as 2 * C * rows floats.
+long bn_ws_rows(long m, long c) {
+    TORCH_CHECK(c >= 8 && c % 8 == 0 && c / 8 <= 256,
+                "bn_num_rblocks requires C % 8 == 0 and 8 <= C <= 2048, "
+                "got C=", c);
+    return bn_num_rblocks(m, (int)c);
+}
+
 // y = [relu](bn(x)); fills sums(2C ws), save_mean/save_rstd/scale/shift(C).
 void bn_fwd(torch::Tensor x, torch::Tensor z, torch::Tensor y,
             torch::Tensor gamma, torch::Tensor beta,
@@ -301,7 +198,7 @@ void bn_fwd(torch::Tensor x, torch::Tensor z, torch::Tensor y,
                 "bn_fwd requires C % 8 == 0 and C <= 2048, got C=", c);
     check_vecf(gamma, c, "gamma"); check_vecf(beta, c, "beta");
     if (train)
-        check_vecf(ws, 2 * c * bn_num_rblocks(m, c), "ws");
+        check_vecf(ws, 2 * c * bn_num_rblocks(m, (int)c), "ws");
     check_vecf(sums, 2 * c, "sums");
     check_vecf(save_mean, c, "save_mean");
     check_vecf(save_rstd, c, "save_rstd");
@@ -348,7 +245,7 @@ void bn_bwd(torch::Tensor x, torch::Tensor z, torch::Tensor dy,
     check_vecf(save_mean, c, "save_mean");
     check_vecf(save_rstd, c, "save_rstd");
     check_vecf(scale, c, "scale"); check_vecf(shift, c, "shift");
-    check_vecf(ws, 2 * c * bn_num_rblocks(m, c), "ws");
+    check_vecf(ws, 2 * c * bn_num_rblocks(m, (int)c), "ws");
     check_vecf(sums, 2 * c, "sums");
     check_vecf(dgamma, c, "dgamma"); check_vecf(dbeta, c, "dbeta");
     check_vecf(pqr, 3 * c, "pqr");
@@ -560,6 +457,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("fused_adamw", &fused_adamw, "fused flat-bucket Adam(W) step");
     mod.def("bn_fwd", &bn_fwd, "fused NHWC bf16 BatchNorm(+ReLU) forward");
     mod.def("bn_bwd", &bn_bwd, "fused NHWC bf16 BatchNorm(+ReLU) backward");
+    mod.def("bn_num_rblocks", &bn_ws_rows,
+            "rows of the BN stage-1 partials workspace for (M, C)");
     mod.def("conv_wrw_ok", &conv_wrw_ok, "3x3 wrw fast-path predicate");
     mod.def("conv_wrw_nsplit", &conv_wrw_nsplit, "wrw workspace splits");
     mod.def("conv_wrw", &conv_wrw, "MFMA 3x3 s1 NHWC weight gradient");

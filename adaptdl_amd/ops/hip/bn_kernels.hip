@@ -24,6 +24,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "kernels.h"
+
 #define WAVE 64
 #define BLOCK 256
 #define MAX_RBLOCKS 1024   // stage-1 reduction grid cap (partials rows)
@@ -400,16 +402,29 @@ static inline unsigned bn_grid(long work_items, int per_block, long cap) {
     return (unsigned)blocks;
 }
 
+// Rows a block covers per grid-stride step: each thread owns one channel
+// octet, so BLOCK threads span BLOCK / (C / VEC) whole rows.
+static inline int bn_rows_per_block(int c) {
+    const int slots = c / VEC;
+    return BLOCK / slots > 0 ? BLOCK / slots : 1;
+}
+
+// Stage-1 (reduce) grid size = rows of the partials workspace.  The ONLY
+// definition: launchers, the bindings' size check and the Python-side
+// allocation all call this.
+extern "C" long bn_num_rblocks(long m, int c) {
+    return bn_grid(m, bn_rows_per_block(c), MAX_RBLOCKS);
+}
+
 extern "C" void launch_bn_fwd(
         const ushort_t* x, const ushort_t* z, ushort_t* y, long m, int c,
         const float* gamma, const float* beta, float* running_mean,
         float* running_var, float momentum, float eps, int train, int relu,
         float* ws, float* sums, float* save_mean, float* save_rstd,
         float* scale, float* shift, hipStream_t s) {
-    const int slots = c / VEC;
-    const int rpb = BLOCK / slots > 0 ? BLOCK / slots : 1;
+    const int rpb = bn_rows_per_block(c);
     if (train) {
-        const unsigned nb = bn_grid(m, rpb, MAX_RBLOCKS);
+        const unsigned nb = (unsigned)bn_num_rblocks(m, c);
         hipLaunchKernelGGL(k_bn_fwd_reduce, dim3(nb), dim3(BLOCK), 0, s,
                            x, m, c, (int)nb, ws);
         hipLaunchKernelGGL(k_bn_reduce_ws, dim3(2 * c), dim3(BLOCK), 0, s,
@@ -437,9 +452,8 @@ extern "C" void launch_bn_bwd(
         const float* scale, const float* shift, int train, int relu,
         float* ws, float* sums, float* dgamma, float* dbeta, float* pqr,
         hipStream_t s) {
-    const int slots = c / VEC;
-    const int rpb = BLOCK / slots > 0 ? BLOCK / slots : 1;
-    const unsigned nb = bn_grid(m, rpb, MAX_RBLOCKS);
+    const int rpb = bn_rows_per_block(c);
+    const unsigned nb = (unsigned)bn_num_rblocks(m, c);
     hipLaunchKernelGGL(k_bn_bwd_reduce, dim3(nb), dim3(BLOCK), 0, s,
                        x, z, dy, m, c, (int)nb, save_mean, save_rstd,
                        scale, shift, relu, ws);

@@ -34,6 +34,8 @@
 #include <hip/hip_bf16.h>
 #include <cstdlib>
 
+#include "kernels.h"
+
 #define WAVE 64
 
 __device__ __forceinline__ unsigned short f2b(float f) {

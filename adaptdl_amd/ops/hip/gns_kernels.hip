@@ -11,8 +11,17 @@
 // Design notes (see /opt/skills/guides/cdna_hip_programming.md):
 // - wavefront = 64; block = 256 threads (4 waves); grid-stride loop capped
 //   at ~2048 blocks (256 CU * 8 blocks) for memory-bound ops (Guideline 11)
-// - float4 vectorized global access (16 B/lane; Guideline 13), with
-//   scalar peel for unaligned segment starts and tails
+// - ONE traversal (stat_pass) serves every statistics kernel: scalar head
+//   up to 16-byte alignment, 16-byte vector body (16 B/lane; Guideline
+//   13), scalar tail.  An element trait (F32 / BF16 / FP16) supplies the
+//   storage type, the vector width and the conversions; a per-op functor
+//   supplies the per-element math.  The kernels are thin extern "C"
+//   wrappers, so their names stay stable for the profiles/ ledger.
+// - two-operand kernels cast both pointers to vector pointers, which is
+//   only valid when they are co-aligned (equal modulo 16 bytes; always
+//   true for bucket-flat segments).  If they are not, that launch takes
+//   the scalar loop for the whole range — a grid-uniform branch, since it
+//   depends on kernel arguments only.
 // - fp64 accumulation per thread -> wave __shfl_down reduce -> LDS partial
 //   per wave -> one global fp64 atomicAdd per block (Guideline 12)
 // - elementwise writes (scale / prev-copy) fused into the same pass so
@@ -20,6 +29,9 @@
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
+#include <hip/hip_fp16.h>
+
+#include "kernels.h"
 
 #define WAVE 64
 #define BLOCK 256
@@ -49,494 +61,245 @@ __device__ __forceinline__ void block_reduce_atomic(double v, double* out) {
     }
 }
 
-// Grid-stride traversal over n floats with float4 vector body.
-// Each functor F provides: double elem(long i) applied per scalar index.
-// We specialize the main kernels directly instead of templating over
-// functors to keep the vector path explicit.
+// ---- element traits: storage type, 16-byte vector, conversions -------
+// (bf16/fp16 buckets: true-low-precision-parameter models; the in-place
+// ops round back with RNE.)
 
-extern "C" __global__ __launch_bounds__(BLOCK) void k_sqsum(
-        const float* __restrict__ x, long n, double* __restrict__ out) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    // Head: scalar until 16-byte aligned.
-    long head = (16 - ((size_t)x & 15)) / 4 & 3;
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        double v = (double)x[j];
-        acc += v * v;
-    }
-    const float4* xv = (const float4*)(x + head);
-    const long nv = (n - head) / 4;
-    for (long j = i; j < nv; j += stride) {
-        float4 v = xv[j];
-        acc += (double)v.x * v.x + (double)v.y * v.y +
-               (double)v.z * v.z + (double)v.w * v.w;
-    }
-    for (long j = head + nv * 4 + i; j < n; j += stride) {
-        double v = (double)x[j];
-        acc += v * v;
-    }
-    block_reduce_atomic(acc, out);
-}
+struct F32 {
+    typedef float elem;
+    typedef __attribute__((ext_vector_type(4))) float vec;
+    static constexpr int W = 4;
+    static __device__ __forceinline__ float to_f(float x) { return x; }
+    static __device__ __forceinline__ float from_f(float f) { return f; }
+};
 
-extern "C" __global__ __launch_bounds__(BLOCK) void k_scale_sqsum(
-        float* __restrict__ x, long n, float scale,
+struct BF16 {
+    typedef unsigned short elem;
+    typedef __attribute__((ext_vector_type(8))) unsigned short vec;
+    static constexpr int W = 8;
+    static __device__ __forceinline__ float to_f(unsigned short h) {
+        union { float f; unsigned u; } c;
+        c.u = ((unsigned)h) << 16;
+        return c.f;
+    }
+    static __device__ __forceinline__ unsigned short from_f(float f) {
+        __hip_bfloat16 h = __float2bfloat16(f);  // RNE
+        return *reinterpret_cast<unsigned short*>(&h);
+    }
+};
+
+struct FP16 {
+    typedef unsigned short elem;
+    typedef __attribute__((ext_vector_type(8))) unsigned short vec;
+    static constexpr int W = 8;
+    static __device__ __forceinline__ float to_f(unsigned short h) {
+        return __half2float(*reinterpret_cast<const __half*>(&h));
+    }
+    static __device__ __forceinline__ unsigned short from_f(float f) {
+        __half h = __float2half_rn(f);
+        return *reinterpret_cast<unsigned short*>(&h);
+    }
+};
+
+// ---- per-op functors -------------------------------------------------
+// apply<T>(a, b) sees one stored element of each operand (b is unused by
+// one-operand ops), returns its fp64 contribution and may rewrite the
+// element named by `writes` (0 = a, 1 = b, -1 = read-only pass).
+
+struct SqSum {  // sum(x^2)
+    static constexpr int operands = 1, writes = -1;
+    template <class T> __device__ __forceinline__ double apply(
+            typename T::elem& x, typename T::elem&) const {
+        double v = (double)T::to_f(x);
+        return v * v;
+    }
+};
+
+struct ScaleSqSum {  // x *= scale; sum(x^2)
+    static constexpr int operands = 1, writes = 0;
+    float scale;
+    template <class T> __device__ __forceinline__ double apply(
+            typename T::elem& x, typename T::elem&) const {
+        float v = T::to_f(x) * scale;
+        x = T::from_f(v);
+        return (double)v * v;
+    }
+};
+
+// sum((cur - prev)^2); prev = cur.  (accumulation microbatch stat)
+struct SqSumDiffUpdate {
+    static constexpr int operands = 2, writes = 1;
+    template <class T> __device__ __forceinline__ double apply(
+            typename T::elem& cur, typename T::elem& prev) const {
+        double d = (double)T::to_f(cur) - (double)T::to_f(prev);
+        prev = cur;
+        return d * d;
+    }
+};
+
+// sum(((cur + prev) / 2)^2)   (differenced single-sample estimator)
+struct SqSumAvg {
+    static constexpr int operands = 2, writes = -1;
+    template <class T> __device__ __forceinline__ double apply(
+            typename T::elem& cur, typename T::elem& prev) const {
+        double a = 0.5 * ((double)T::to_f(cur) + (double)T::to_f(prev));
+        return a * a;
+    }
+};
+
+// sum((g / pinv)^2), pinv = sqrt(v) * inv_corr_sqrt + eps (Adam
+// precondition; reference AdamGradientNoiseScale._calculate_preconditioner)
+struct PrecondSqSum {
+    static constexpr int operands = 2, writes = -1;
+    float ics, eps;
+    template <class T> __device__ __forceinline__ double apply(
+            typename T::elem& g, typename T::elem& v) const {
+        float pinv = sqrtf(T::to_f(v)) * ics + eps;
+        double q = (double)(T::to_f(g) / pinv);
+        return q * q;
+    }
+};
+
+// ---- the traversal ---------------------------------------------------
+// Grid-stride pass of functor F over n elements of a (and b): scalar head
+// until a is 16-byte aligned, T::W-wide vector body, scalar tail, then one
+// fp64 atomic per block into out.  A / B are T::elem or const T::elem; an
+// operand is stored through only if F::writes names it.
+template <class T, class F, class A, class B>
+__device__ __forceinline__ void stat_pass(
+        A* __restrict__ a, B* __restrict__ b, long n, const F f,
         double* __restrict__ out) {
+    typedef typename T::elem E;
+    typedef typename T::vec V;
+    constexpr int W = T::W;
     double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
     const long stride = (long)gridDim.x * BLOCK;
-    long head = (16 - ((size_t)x & 15)) / 4 & 3;
+
+    auto scalar = [&](long j) {
+        E ea = a[j], eb = E();
+        if constexpr (F::operands == 2) eb = b[j];
+        acc += f.template apply<T>(ea, eb);
+        if constexpr (F::writes == 0) a[j] = ea;
+        if constexpr (F::writes == 1) b[j] = eb;
+    };
+
+    long head = (16 - ((size_t)a & 15)) / sizeof(E) & (W - 1);
+    if constexpr (F::operands == 2) {
+        // Mis-coaligned operands: the whole range is "head" (scalar).
+        if ((((size_t)a ^ (size_t)b) & 15) != 0) head = n;
+    }
     if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        float v = x[j] * scale;
-        x[j] = v;
-        acc += (double)v * v;
-    }
-    float4* xv = (float4*)(x + head);
-    const long nv = (n - head) / 4;
+    for (long j = i; j < head; j += stride) scalar(j);
+
+    const long nv = (n - head) / W;
     for (long j = i; j < nv; j += stride) {
-        float4 v = xv[j];
-        v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
-        xv[j] = v;
-        acc += (double)v.x * v.x + (double)v.y * v.y +
-               (double)v.z * v.z + (double)v.w * v.w;
-    }
-    for (long j = head + nv * 4 + i; j < n; j += stride) {
-        float v = x[j] * scale;
-        x[j] = v;
-        acc += (double)v * v;
-    }
-    block_reduce_atomic(acc, out);
-}
-
-// out += sum((cur - prev)^2); prev = cur.  (accumulation microbatch stat)
-extern "C" __global__ __launch_bounds__(BLOCK) void k_sqsum_diff_update(
-        const float* __restrict__ cur, float* __restrict__ prev, long n,
-        double* __restrict__ out) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    // cur and prev share alignment (same bucket layout).
-    long head = (16 - ((size_t)cur & 15)) / 4 & 3;
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        float c = cur[j];
-        double d = (double)c - (double)prev[j];
-        prev[j] = c;
-        acc += d * d;
-    }
-    const float4* cv = (const float4*)(cur + head);
-    float4* pv = (float4*)(prev + head);
-    const long nv = (n - head) / 4;
-    for (long j = i; j < nv; j += stride) {
-        float4 c = cv[j];
-        float4 p = pv[j];
-        double d0 = (double)c.x - (double)p.x, d1 = (double)c.y - (double)p.y;
-        double d2 = (double)c.z - (double)p.z, d3 = (double)c.w - (double)p.w;
-        pv[j] = c;
-        acc += d0 * d0 + d1 * d1 + d2 * d2 + d3 * d3;
-    }
-    for (long j = head + nv * 4 + i; j < n; j += stride) {
-        float c = cur[j];
-        double d = (double)c - (double)prev[j];
-        prev[j] = c;
-        acc += d * d;
-    }
-    block_reduce_atomic(acc, out);
-}
-
-// out += sum(((cur + prev) / 2)^2)   (differenced single-sample estimator)
-extern "C" __global__ __launch_bounds__(BLOCK) void k_sqsum_avg(
-        const float* __restrict__ cur, const float* __restrict__ prev,
-        long n, double* __restrict__ out) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    long head = (16 - ((size_t)cur & 15)) / 4 & 3;
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        double a = 0.5 * ((double)cur[j] + (double)prev[j]);
-        acc += a * a;
-    }
-    const float4* cv = (const float4*)(cur + head);
-    const float4* pv = (const float4*)(prev + head);
-    const long nv = (n - head) / 4;
-    for (long j = i; j < nv; j += stride) {
-        float4 c = cv[j];
-        float4 p = pv[j];
-        double a0 = 0.5 * ((double)c.x + p.x), a1 = 0.5 * ((double)c.y + p.y);
-        double a2 = 0.5 * ((double)c.z + p.z), a3 = 0.5 * ((double)c.w + p.w);
-        acc += a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3;
-    }
-    for (long j = head + nv * 4 + i; j < n; j += stride) {
-        double a = 0.5 * ((double)cur[j] + (double)prev[j]);
-        acc += a * a;
-    }
-    block_reduce_atomic(acc, out);
-}
-
-// ---- bf16 variants (true-bf16-parameter models).
-// Same structure as the f32 kernels: grid-stride with a 16-byte-aligned
-// 8-wide vector body (8 bf16 = 16 B), fp64 accumulation; the in-place
-// variants round back to bf16 with RNE.
-
-typedef __attribute__((ext_vector_type(8))) unsigned short us16x8;
-
-__device__ __forceinline__ float bf2f(unsigned short h) {
-    union { float f; unsigned u; } c;
-    c.u = ((unsigned)h) << 16;
-    return c.f;
-}
-
-__device__ __forceinline__ unsigned short f2b(float f) {
-    __hip_bfloat16 h = __float2bfloat16(f);  // RNE
-    return *reinterpret_cast<unsigned short*>(&h);
-}
-
-#define BF16_HEAD(ptr) ((16 - ((size_t)(ptr) & 15)) / 2 & 7)
-
-extern "C" __global__ __launch_bounds__(BLOCK) void k_sqsum_bf16(
-        const unsigned short* __restrict__ x, long n,
-        double* __restrict__ out) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    long head = BF16_HEAD(x);
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        double v = (double)bf2f(x[j]);
-        acc += v * v;
-    }
-    const us16x8* xv = (const us16x8*)(x + head);
-    const long nv = (n - head) / 8;
-    for (long j = i; j < nv; j += stride) {
-        us16x8 v = xv[j];
+        V va = ((const V*)(a + head))[j], vb = V();
+        if constexpr (F::operands == 2) vb = ((const V*)(b + head))[j];
         #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            double q = (double)bf2f(v[k]);
-            acc += q * q;
+        for (int k = 0; k < W; ++k) {
+            E ea = va[k], eb = vb[k];
+            acc += f.template apply<T>(ea, eb);
+            va[k] = ea;
+            vb[k] = eb;
         }
+        if constexpr (F::writes == 0) ((V*)(a + head))[j] = va;
+        if constexpr (F::writes == 1) ((V*)(b + head))[j] = vb;
     }
-    for (long j = head + nv * 8 + i; j < n; j += stride) {
-        double v = (double)bf2f(x[j]);
-        acc += v * v;
-    }
+
+    for (long j = head + nv * W + i; j < n; j += stride) scalar(j);
     block_reduce_atomic(acc, out);
 }
 
-extern "C" __global__ __launch_bounds__(BLOCK) void k_scale_sqsum_bf16(
-        unsigned short* __restrict__ x, long n, float scale,
-        double* __restrict__ out) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    long head = BF16_HEAD(x);
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        float v = bf2f(x[j]) * scale;
-        x[j] = f2b(v);
-        acc += (double)v * v;
-    }
-    us16x8* xv = (us16x8*)(x + head);
-    const long nv = (n - head) / 8;
-    for (long j = i; j < nv; j += stride) {
-        us16x8 v = xv[j];
-        #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            float q = bf2f(v[k]) * scale;
-            v[k] = f2b(q);
-            acc += (double)q * q;
-        }
-        xv[j] = v;
-    }
-    for (long j = head + nv * 8 + i; j < n; j += stride) {
-        float v = bf2f(x[j]) * scale;
-        x[j] = f2b(v);
-        acc += (double)v * v;
-    }
-    block_reduce_atomic(acc, out);
+template <class T, class F, class A>
+__device__ __forceinline__ void stat_pass(
+        A* __restrict__ a, long n, const F f, double* __restrict__ out) {
+    stat_pass<T>(a, (const typename T::elem*)nullptr, n, f, out);
 }
 
-extern "C" __global__ __launch_bounds__(BLOCK)
-void k_sqsum_diff_update_bf16(
+// ---- statistics kernels (names are the profiles/ ledger keys) --------
+
+#define STAT_KERNEL extern "C" __global__ __launch_bounds__(BLOCK) void
+
+STAT_KERNEL k_sqsum(const float* __restrict__ x, long n,
+                    double* __restrict__ out) {
+    stat_pass<F32>(x, n, SqSum{}, out);
+}
+STAT_KERNEL k_sqsum_bf16(const unsigned short* __restrict__ x, long n,
+                         double* __restrict__ out) {
+    stat_pass<BF16>(x, n, SqSum{}, out);
+}
+STAT_KERNEL k_sqsum_fp16(const unsigned short* __restrict__ x, long n,
+                         double* __restrict__ out) {
+    stat_pass<FP16>(x, n, SqSum{}, out);
+}
+
+STAT_KERNEL k_scale_sqsum(float* __restrict__ x, long n, float scale,
+                          double* __restrict__ out) {
+    stat_pass<F32>(x, n, ScaleSqSum{scale}, out);
+}
+STAT_KERNEL k_scale_sqsum_bf16(unsigned short* __restrict__ x, long n,
+                               float scale, double* __restrict__ out) {
+    stat_pass<BF16>(x, n, ScaleSqSum{scale}, out);
+}
+STAT_KERNEL k_scale_sqsum_fp16(unsigned short* __restrict__ x, long n,
+                               float scale, double* __restrict__ out) {
+    stat_pass<FP16>(x, n, ScaleSqSum{scale}, out);
+}
+
+STAT_KERNEL k_sqsum_diff_update(const float* __restrict__ cur,
+                                float* __restrict__ prev, long n,
+                                double* __restrict__ out) {
+    stat_pass<F32>(cur, prev, n, SqSumDiffUpdate{}, out);
+}
+STAT_KERNEL k_sqsum_diff_update_bf16(
         const unsigned short* __restrict__ cur,
         unsigned short* __restrict__ prev, long n,
         double* __restrict__ out) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    long head = BF16_HEAD(cur);
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        unsigned short c = cur[j];
-        double d = (double)bf2f(c) - (double)bf2f(prev[j]);
-        prev[j] = c;
-        acc += d * d;
-    }
-    const us16x8* cv = (const us16x8*)(cur + head);
-    us16x8* pv = (us16x8*)(prev + head);
-    const long nv = (n - head) / 8;
-    for (long j = i; j < nv; j += stride) {
-        us16x8 c = cv[j];
-        us16x8 p = pv[j];
-        #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            double d = (double)bf2f(c[k]) - (double)bf2f(p[k]);
-            acc += d * d;
-        }
-        pv[j] = c;
-    }
-    for (long j = head + nv * 8 + i; j < n; j += stride) {
-        unsigned short c = cur[j];
-        double d = (double)bf2f(c) - (double)bf2f(prev[j]);
-        prev[j] = c;
-        acc += d * d;
-    }
-    block_reduce_atomic(acc, out);
+    stat_pass<BF16>(cur, prev, n, SqSumDiffUpdate{}, out);
 }
-
-extern "C" __global__ __launch_bounds__(BLOCK) void k_sqsum_avg_bf16(
+STAT_KERNEL k_sqsum_diff_update_fp16(
         const unsigned short* __restrict__ cur,
-        const unsigned short* __restrict__ prev, long n,
+        unsigned short* __restrict__ prev, long n,
         double* __restrict__ out) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    long head = BF16_HEAD(cur);
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        double a = 0.5 * ((double)bf2f(cur[j]) + (double)bf2f(prev[j]));
-        acc += a * a;
-    }
-    const us16x8* cv = (const us16x8*)(cur + head);
-    const us16x8* pv = (const us16x8*)(prev + head);
-    const long nv = (n - head) / 8;
-    for (long j = i; j < nv; j += stride) {
-        us16x8 c = cv[j];
-        us16x8 p = pv[j];
-        #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            double a = 0.5 * ((double)bf2f(c[k]) + (double)bf2f(p[k]));
-            acc += a * a;
-        }
-    }
-    for (long j = head + nv * 8 + i; j < n; j += stride) {
-        double a = 0.5 * ((double)bf2f(cur[j]) + (double)bf2f(prev[j]));
-        acc += a * a;
-    }
-    block_reduce_atomic(acc, out);
+    stat_pass<FP16>(cur, prev, n, SqSumDiffUpdate{}, out);
 }
 
-// ---- fp16 variants: identical structure to the bf16 set, with
-// __half conversions (fp16-parameter models).
-
-#include <hip/hip_fp16.h>
-
-__device__ __forceinline__ float hf2f(unsigned short h) {
-    __half v = *reinterpret_cast<const __half*>(&h);
-    return __half2float(v);
+STAT_KERNEL k_sqsum_avg(const float* __restrict__ cur,
+                        const float* __restrict__ prev, long n,
+                        double* __restrict__ out) {
+    stat_pass<F32>(cur, prev, n, SqSumAvg{}, out);
+}
+STAT_KERNEL k_sqsum_avg_bf16(const unsigned short* __restrict__ cur,
+                             const unsigned short* __restrict__ prev,
+                             long n, double* __restrict__ out) {
+    stat_pass<BF16>(cur, prev, n, SqSumAvg{}, out);
+}
+STAT_KERNEL k_sqsum_avg_fp16(const unsigned short* __restrict__ cur,
+                             const unsigned short* __restrict__ prev,
+                             long n, double* __restrict__ out) {
+    stat_pass<FP16>(cur, prev, n, SqSumAvg{}, out);
 }
 
-__device__ __forceinline__ unsigned short f2hf(float f) {
-    __half h = __float2half_rn(f);
-    return *reinterpret_cast<unsigned short*>(&h);
-}
-
-#define DEF_SQSUM_16(SUFFIX, TO_F, FROM_F) \
-extern "C" __global__ __launch_bounds__(BLOCK) void k_sqsum_##SUFFIX( \
-        const unsigned short* __restrict__ x, long n, \
-        double* __restrict__ out) { \
-    double acc = 0.0; \
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x; \
-    const long stride = (long)gridDim.x * BLOCK; \
-    long head = BF16_HEAD(x); \
-    if (head > n) head = n; \
-    for (long j = i; j < head; j += stride) { \
-        double v = (double)TO_F(x[j]); acc += v * v; } \
-    const us16x8* xv = (const us16x8*)(x + head); \
-    const long nv = (n - head) / 8; \
-    for (long j = i; j < nv; j += stride) { \
-        us16x8 v = xv[j]; \
-        _Pragma("unroll") for (int k = 0; k < 8; ++k) { \
-            double q = (double)TO_F(v[k]); acc += q * q; } } \
-    for (long j = head + nv * 8 + i; j < n; j += stride) { \
-        double v = (double)TO_F(x[j]); acc += v * v; } \
-    block_reduce_atomic(acc, out); \
-} \
-extern "C" __global__ __launch_bounds__(BLOCK) \
-void k_scale_sqsum_##SUFFIX( \
-        unsigned short* __restrict__ x, long n, float scale, \
-        double* __restrict__ out) { \
-    double acc = 0.0; \
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x; \
-    const long stride = (long)gridDim.x * BLOCK; \
-    long head = BF16_HEAD(x); \
-    if (head > n) head = n; \
-    for (long j = i; j < head; j += stride) { \
-        float v = TO_F(x[j]) * scale; x[j] = FROM_F(v); \
-        acc += (double)v * v; } \
-    us16x8* xv = (us16x8*)(x + head); \
-    const long nv = (n - head) / 8; \
-    for (long j = i; j < nv; j += stride) { \
-        us16x8 v = xv[j]; \
-        _Pragma("unroll") for (int k = 0; k < 8; ++k) { \
-            float q = TO_F(v[k]) * scale; v[k] = FROM_F(q); \
-            acc += (double)q * q; } \
-        xv[j] = v; } \
-    for (long j = head + nv * 8 + i; j < n; j += stride) { \
-        float v = TO_F(x[j]) * scale; x[j] = FROM_F(v); \
-        acc += (double)v * v; } \
-    block_reduce_atomic(acc, out); \
-} \
-extern "C" __global__ __launch_bounds__(BLOCK) \
-void k_sqsum_diff_update_##SUFFIX( \
-        const unsigned short* __restrict__ cur, \
-        unsigned short* __restrict__ prev, long n, \
-        double* __restrict__ out) { \
-    double acc = 0.0; \
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x; \
-    const long stride = (long)gridDim.x * BLOCK; \
-    long head = BF16_HEAD(cur); \
-    if (head > n) head = n; \
-    for (long j = i; j < head; j += stride) { \
-        unsigned short c = cur[j]; \
-        double d = (double)TO_F(c) - (double)TO_F(prev[j]); \
-        prev[j] = c; acc += d * d; } \
-    const us16x8* cv = (const us16x8*)(cur + head); \
-    us16x8* pv = (us16x8*)(prev + head); \
-    const long nv = (n - head) / 8; \
-    for (long j = i; j < nv; j += stride) { \
-        us16x8 c = cv[j]; us16x8 p = pv[j]; \
-        _Pragma("unroll") for (int k = 0; k < 8; ++k) { \
-            double d = (double)TO_F(c[k]) - (double)TO_F(p[k]); \
-            acc += d * d; } \
-        pv[j] = c; } \
-    for (long j = head + nv * 8 + i; j < n; j += stride) { \
-        unsigned short c = cur[j]; \
-        double d = (double)TO_F(c) - (double)TO_F(prev[j]); \
-        prev[j] = c; acc += d * d; } \
-    block_reduce_atomic(acc, out); \
-} \
-extern "C" __global__ __launch_bounds__(BLOCK) \
-void k_sqsum_avg_##SUFFIX( \
-        const unsigned short* __restrict__ cur, \
-        const unsigned short* __restrict__ prev, long n, \
-        double* __restrict__ out) { \
-    double acc = 0.0; \
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x; \
-    const long stride = (long)gridDim.x * BLOCK; \
-    long head = BF16_HEAD(cur); \
-    if (head > n) head = n; \
-    for (long j = i; j < head; j += stride) { \
-        double a = 0.5 * ((double)TO_F(cur[j]) + (double)TO_F(prev[j])); \
-        acc += a * a; } \
-    const us16x8* cv = (const us16x8*)(cur + head); \
-    const us16x8* pv = (const us16x8*)(prev + head); \
-    const long nv = (n - head) / 8; \
-    for (long j = i; j < nv; j += stride) { \
-        us16x8 c = cv[j]; us16x8 p = pv[j]; \
-        _Pragma("unroll") for (int k = 0; k < 8; ++k) { \
-            double a = 0.5 * ((double)TO_F(c[k]) + (double)TO_F(p[k])); \
-            acc += a * a; } } \
-    for (long j = head + nv * 8 + i; j < n; j += stride) { \
-        double a = 0.5 * ((double)TO_F(cur[j]) + (double)TO_F(prev[j])); \
-        acc += a * a; } \
-    block_reduce_atomic(acc, out); \
-}
-
-DEF_SQSUM_16(fp16, hf2f, f2hf)
-
-// Shared body for the Adam-preconditioned sum-of-squares:
-//   acc = sum((g / pinv)^2), pinv = sqrt(v) * inv_corr_sqrt + eps
-// float4-vectorized when g and v are co-aligned (bucket-flat segments
-// share offsets, so they always are in practice).
-__device__ __forceinline__ double precond_sqsum_body(
-        const float* __restrict__ g, const float* __restrict__ v, long n,
-        float ics, float eps) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    if (((size_t)g & 15) != ((size_t)v & 15)) {  // mis-coaligned: scalar
-        for (long j = i; j < n; j += stride) {
-            float pinv = sqrtf(v[j]) * ics + eps;
-            double q = (double)(g[j] / pinv);
-            acc += q * q;
-        }
-        return acc;
-    }
-    long head = (16 - ((size_t)g & 15)) / 4 & 3;
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        float pinv = sqrtf(v[j]) * ics + eps;
-        double q = (double)(g[j] / pinv);
-        acc += q * q;
-    }
-    const float4* gv = (const float4*)(g + head);
-    const float4* vv = (const float4*)(v + head);
-    const long nv = (n - head) / 4;
-    for (long j = i; j < nv; j += stride) {
-        float4 gg = gv[j];
-        float4 s = vv[j];
-        double q0 = (double)(gg.x / (sqrtf(s.x) * ics + eps));
-        double q1 = (double)(gg.y / (sqrtf(s.y) * ics + eps));
-        double q2 = (double)(gg.z / (sqrtf(s.z) * ics + eps));
-        double q3 = (double)(gg.w / (sqrtf(s.w) * ics + eps));
-        acc += q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3;
-    }
-    for (long j = head + nv * 4 + i; j < n; j += stride) {
-        float pinv = sqrtf(v[j]) * ics + eps;
-        double q = (double)(g[j] / pinv);
-        acc += q * q;
-    }
-    return acc;
-}
-
-__device__ __forceinline__ double plain_sqsum_body(
-        const float* __restrict__ x, long n) {
-    double acc = 0.0;
-    long i = (long)blockIdx.x * BLOCK + threadIdx.x;
-    const long stride = (long)gridDim.x * BLOCK;
-    long head = (16 - ((size_t)x & 15)) / 4 & 3;
-    if (head > n) head = n;
-    for (long j = i; j < head; j += stride) {
-        double q = (double)x[j];
-        acc += q * q;
-    }
-    const float4* xv = (const float4*)(x + head);
-    const long nv = (n - head) / 4;
-    for (long j = i; j < nv; j += stride) {
-        float4 c = xv[j];
-        acc += (double)c.x * c.x + (double)c.y * c.y
-             + (double)c.z * c.z + (double)c.w * c.w;
-    }
-    for (long j = head + nv * 4 + i; j < n; j += stride) {
-        double q = (double)x[j];
-        acc += q * q;
-    }
-    return acc;
-}
-
-// out += sum((g / pinv)^2), pinv = sqrt(v / corr) + eps (Adam precondition;
-// reference AdamGradientNoiseScale._calculate_preconditioner)
-extern "C" __global__ __launch_bounds__(BLOCK) void k_precond_sqsum(
-        const float* __restrict__ g, const float* __restrict__ v, long n,
-        float inv_corr_sqrt, float eps, double* __restrict__ out) {
-    double acc = precond_sqsum_body(g, v, n, inv_corr_sqrt, eps);
-    block_reduce_atomic(acc, out);
+STAT_KERNEL k_precond_sqsum(const float* __restrict__ g,
+                            const float* __restrict__ v, long n,
+                            float inv_corr_sqrt, float eps,
+                            double* __restrict__ out) {
+    stat_pass<F32>(g, v, n, PrecondSqSum{inv_corr_sqrt, eps}, out);
 }
 
 // hipGraph-capturable variant: the bias-correction scalars live in
 // DEVICE memory (pc = {inv_corr_sqrt, eps, use_precond, unused}) so a
 // captured graph picks up each step's values instead of baking them in.
 // use_precond == 0 -> identity preconditioner (warmup steps).
-extern "C" __global__ __launch_bounds__(BLOCK) void k_precond_sqsum_dev(
-        const float* __restrict__ g, const float* __restrict__ v, long n,
-        const float* __restrict__ pc, double* __restrict__ out) {
-    double acc = (pc[2] != 0.f)
-        ? precond_sqsum_body(g, v, n, pc[0], pc[1])
-        : plain_sqsum_body(g, n);
-    block_reduce_atomic(acc, out);
+STAT_KERNEL k_precond_sqsum_dev(const float* __restrict__ g,
+                                const float* __restrict__ v, long n,
+                                const float* __restrict__ pc,
+                                double* __restrict__ out) {
+    if (pc[2] != 0.f)
+        stat_pass<F32>(g, v, n, PrecondSqSum{pc[0], pc[1]}, out);
+    else
+        stat_pass<F32>(g, n, SqSum{}, out);
 }
 
 // ---- fused flat-bucket optimizers -----------------------------------
@@ -596,115 +359,93 @@ static inline dim3 grid_for(long n) {
     return dim3((unsigned)blocks);
 }
 
-extern "C" void launch_sqsum(const float* x, long n, double* out,
-                             hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum, grid_for(n), dim3(BLOCK), 0, s, x, n, out);
+// One launch of kernel K over n elements on stream s.
+template <class K, class... Args>
+static inline void launch(K kernel, long n, hipStream_t s, Args... args) {
+    hipLaunchKernelGGL(kernel, grid_for(n), dim3(BLOCK), 0, s, args...);
 }
 
-extern "C" void launch_scale_sqsum(float* x, long n, float scale,
-                                   double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_scale_sqsum, grid_for(n), dim3(BLOCK), 0, s, x, n,
-                       scale, out);
+typedef unsigned short u16;
+
+extern "C" void launch_sqsum(StatDtype dtype, const void* x, long n, double* out,
+                  hipStream_t s) {
+    switch (dtype) {
+    case STAT_F32: launch(k_sqsum, n, s, (const float*)x, n, out); break;
+    case STAT_BF16: launch(k_sqsum_bf16, n, s, (const u16*)x, n, out); break;
+    case STAT_FP16: launch(k_sqsum_fp16, n, s, (const u16*)x, n, out); break;
+    }
 }
 
-extern "C" void launch_sqsum_diff_update(const float* cur, float* prev,
-                                         long n, double* out,
-                                         hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum_diff_update, grid_for(n), dim3(BLOCK), 0, s,
-                       cur, prev, n, out);
+extern "C" void launch_scale_sqsum(StatDtype dtype, void* x, long n, float scale,
+                        double* out, hipStream_t s) {
+    switch (dtype) {
+    case STAT_F32:
+        launch(k_scale_sqsum, n, s, (float*)x, n, scale, out); break;
+    case STAT_BF16:
+        launch(k_scale_sqsum_bf16, n, s, (u16*)x, n, scale, out); break;
+    case STAT_FP16:
+        launch(k_scale_sqsum_fp16, n, s, (u16*)x, n, scale, out); break;
+    }
 }
 
-extern "C" void launch_sqsum_avg(const float* cur, const float* prev, long n,
-                                 double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum_avg, grid_for(n), dim3(BLOCK), 0, s, cur,
-                       prev, n, out);
+extern "C" void launch_sqsum_diff_update(StatDtype dtype, const void* cur, void* prev,
+                              long n, double* out, hipStream_t s) {
+    switch (dtype) {
+    case STAT_F32:
+        launch(k_sqsum_diff_update, n, s, (const float*)cur, (float*)prev,
+               n, out);
+        break;
+    case STAT_BF16:
+        launch(k_sqsum_diff_update_bf16, n, s, (const u16*)cur, (u16*)prev,
+               n, out);
+        break;
+    case STAT_FP16:
+        launch(k_sqsum_diff_update_fp16, n, s, (const u16*)cur, (u16*)prev,
+               n, out);
+        break;
+    }
+}
+
+extern "C" void launch_sqsum_avg(StatDtype dtype, const void* cur, const void* prev,
+                      long n, double* out, hipStream_t s) {
+    switch (dtype) {
+    case STAT_F32:
+        launch(k_sqsum_avg, n, s, (const float*)cur, (const float*)prev, n,
+               out);
+        break;
+    case STAT_BF16:
+        launch(k_sqsum_avg_bf16, n, s, (const u16*)cur, (const u16*)prev, n,
+               out);
+        break;
+    case STAT_FP16:
+        launch(k_sqsum_avg_fp16, n, s, (const u16*)cur, (const u16*)prev, n,
+               out);
+        break;
+    }
 }
 
 extern "C" void launch_precond_sqsum(const float* g, const float* v, long n,
-                                     float inv_corr_sqrt, float eps,
-                                     double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_precond_sqsum, grid_for(n), dim3(BLOCK), 0, s, g, v,
-                       n, inv_corr_sqrt, eps, out);
+                          float inv_corr_sqrt, float eps, double* out,
+                          hipStream_t s) {
+    launch(k_precond_sqsum, n, s, g, v, n, inv_corr_sqrt, eps, out);
 }
 
-extern "C" void launch_sqsum_bf16(const unsigned short* x, long n,
-                                  double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum_bf16, grid_for(n), dim3(BLOCK), 0, s, x, n,
-                       out);
+extern "C" void launch_precond_sqsum_dev(const float* g, const float* v, long n,
+                              const float* pc, double* out, hipStream_t s) {
+    launch(k_precond_sqsum_dev, n, s, g, v, n, pc, out);
 }
 
-extern "C" void launch_scale_sqsum_bf16(unsigned short* x, long n,
-                                        float scale, double* out,
-                                        hipStream_t s) {
-    hipLaunchKernelGGL(k_scale_sqsum_bf16, grid_for(n), dim3(BLOCK), 0, s,
-                       x, n, scale, out);
+extern "C" void launch_fused_sgd(float* p, const float* g, float* m, long n, float lr,
+                      float momentum, float weight_decay, float dampening,
+                      int nesterov, int has_momentum, hipStream_t s) {
+    launch(k_fused_sgd, n, s, p, g, m, n, lr, momentum, weight_decay,
+           dampening, nesterov, has_momentum);
 }
 
-extern "C" void launch_sqsum_diff_update_bf16(const unsigned short* cur,
-                                              unsigned short* prev, long n,
-                                              double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum_diff_update_bf16, grid_for(n), dim3(BLOCK),
-                       0, s, cur, prev, n, out);
-}
-
-extern "C" void launch_sqsum_avg_bf16(const unsigned short* cur,
-                                      const unsigned short* prev, long n,
-                                      double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum_avg_bf16, grid_for(n), dim3(BLOCK), 0, s,
-                       cur, prev, n, out);
-}
-
-extern "C" void launch_sqsum_fp16(const unsigned short* x, long n,
-                                  double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum_fp16, grid_for(n), dim3(BLOCK), 0, s, x, n,
-                       out);
-}
-
-extern "C" void launch_scale_sqsum_fp16(unsigned short* x, long n,
-                                        float scale, double* out,
-                                        hipStream_t s) {
-    hipLaunchKernelGGL(k_scale_sqsum_fp16, grid_for(n), dim3(BLOCK), 0, s,
-                       x, n, scale, out);
-}
-
-extern "C" void launch_sqsum_diff_update_fp16(const unsigned short* cur,
-                                              unsigned short* prev, long n,
-                                              double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum_diff_update_fp16, grid_for(n), dim3(BLOCK),
-                       0, s, cur, prev, n, out);
-}
-
-extern "C" void launch_sqsum_avg_fp16(const unsigned short* cur,
-                                      const unsigned short* prev, long n,
-                                      double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_sqsum_avg_fp16, grid_for(n), dim3(BLOCK), 0, s,
-                       cur, prev, n, out);
-}
-
-extern "C" void launch_precond_sqsum_dev(const float* g, const float* v,
-                                         long n, const float* pc,
-                                         double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_precond_sqsum_dev, grid_for(n), dim3(BLOCK), 0, s,
-                       g, v, n, pc, out);
-}
-
-extern "C" void launch_fused_sgd(float* p, const float* g, float* m, long n,
-                                 float lr, float momentum,
-                                 float weight_decay, float dampening,
-                                 int nesterov, int has_momentum,
-                                 hipStream_t s) {
-    hipLaunchKernelGGL(k_fused_sgd, grid_for(n), dim3(BLOCK), 0, s, p, g, m,
-                       n, lr, momentum, weight_decay, dampening, nesterov,
-                       has_momentum);
-}
-
-extern "C" void launch_fused_adamw(float* p, const float* g, float* m,
-                                   float* v, long n, float lr, float beta1,
-                                   float beta2, float eps,
-                                   float weight_decay, float bias1,
-                                   float bias2, int adam_mode,
-                                   hipStream_t s) {
-    hipLaunchKernelGGL(k_fused_adamw, grid_for(n), dim3(BLOCK), 0, s, p, g,
-                       m, v, n, lr, beta1, beta2, eps, weight_decay, bias1,
-                       bias2, adam_mode);
+extern "C" void launch_fused_adamw(float* p, const float* g, float* m, float* v,
+                        long n, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, float bias1,
+                        float bias2, int adam_mode, hipStream_t s) {
+    launch(k_fused_adamw, n, s, p, g, m, v, n, lr, beta1, beta2, eps,
+           weight_decay, bias1, bias2, adam_mode);
 }

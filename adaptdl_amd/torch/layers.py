@@ -23,12 +23,6 @@ import torch.nn.functional as F
 from adaptdl_amd import ops
 
 
-def _num_rblocks(m, c):
-    """Mirror of bn_kernels.hip stage-1 grid sizing (partials rows)."""
-    rpb = max(256 // (c // 8), 1)
-    return max(min((m + rpb - 1) // rpb, 1024), 1)
-
-
 def _hip_bn_ok(x):
     c = x.shape[1] if x.dim() == 4 else 0
     return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and
@@ -46,7 +40,7 @@ class _FusedBNFunction(torch.autograd.Function):
         c = x.shape[1]
         m = x.numel() // c
         opt = dict(dtype=torch.float32, device=x.device)
-        ws = torch.empty(2 * c * _num_rblocks(m, c), **opt) \
+        ws = torch.empty(2 * c * ext.bn_num_rblocks(m, c), **opt) \
             if training else torch.empty(0, **opt)
         sums = torch.empty(2 * c, **opt)
         save_mean = torch.empty(c, **opt)
@@ -79,7 +73,7 @@ class _FusedBNFunction(torch.autograd.Function):
         c = x.shape[1]
         m = x.numel() // c
         opt = dict(dtype=torch.float32, device=x.device)
-        ws = torch.empty(2 * c * _num_rblocks(m, c), **opt)
+        ws = torch.empty(2 * c * ext.bn_num_rblocks(m, c), **opt)
         sums = torch.empty(2 * c, **opt)
         dgamma = torch.empty(c, **opt)
         dbeta = torch.empty(c, **opt)

@@ -119,6 +119,70 @@ def test_precond_sqsum_dev(n, off):
     assert torch.allclose(out2, g.double().pow(2).sum(), rtol=1e-10)
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16,
+                                   torch.float16])
+@pytest.mark.parametrize("n", [17, 4097])
+def test_two_operand_mixed_alignment(n, dtype):
+    """cur and prev that differ modulo 16 bytes must take the scalar
+    path (no vector cast of the mis-coaligned operand).  n=17 is all
+    head/tail; n=4097 would be head + multi-block body + 1-element tail
+    for co-aligned operands."""
+    torch.manual_seed(n + 57)
+    poff = 2 if dtype == torch.float32 else 3
+    cur = torch.randn(n + 1, device="cuda").to(dtype)[1:]
+    prev = torch.randn(n + poff, device="cuda").to(dtype)[poff:]
+    assert (cur.data_ptr() - prev.data_ptr()) % 16 != 0
+    cur0, prev0 = cur.clone(), prev.clone()
+    rtol = 1e-12 if dtype == torch.float32 else 1e-10
+
+    out = torch.zeros((), dtype=torch.float64, device="cuda")
+    ops.sqsum_avg(cur, prev, out)
+    ref = ((cur0.double() + prev0.double()) / 2).pow(2).sum()
+    assert torch.allclose(out, ref, rtol=rtol, atol=1e-10)
+    assert torch.equal(cur, cur0) and torch.equal(prev, prev0)
+
+    out = torch.zeros((), dtype=torch.float64, device="cuda")
+    ops.sqsum_diff_update(cur, prev, out)
+    ref = (cur0.double() - prev0.double()).pow(2).sum()
+    assert torch.allclose(out, ref, rtol=rtol, atol=1e-10)
+    assert torch.equal(prev, cur0)  # prev <- cur, bit for bit
+    assert torch.equal(cur, cur0)   # cur untouched
+
+
+def test_precond_sqsum_dev_mixed_alignment():
+    """g and v that differ modulo 16 bytes: scalar path, same result."""
+    n = 1023
+    torch.manual_seed(n + 58)
+    g = _rand(n, 1)
+    v = torch.rand(n + 2, device="cuda")[2:]
+    assert (g.data_ptr() - v.data_ptr()) % 16 != 0
+    beta2, eps, step = 0.999, 1e-8, 42
+    pc = torch.zeros(4, dtype=torch.float32, device="cuda")
+    ops.set_precond_scalars(pc, beta2, eps, step)
+    out = torch.zeros((), dtype=torch.float64, device="cuda")
+    ops.precond_sqsum_dev(g, v, pc, out)
+    corr = 1 - beta2 ** step
+    pinv = (v.double() / corr).sqrt() + eps
+    ref = (g.double() / pinv).pow(2).sum()
+    assert torch.allclose(out, ref, rtol=1e-5)
+
+
+@pytest.mark.parametrize("m,c", [(1, 8), (256, 8), (32768, 64),
+                                 (32768, 512), (10 ** 6, 2048)])
+def test_bn_num_rblocks(m, c):
+    """The one C++ definition of the BN stage-1 partials-row count (it
+    sizes the workspace and the stage-1 grid) vs the closed form; the
+    last case reaches the 1024-row cap."""
+    rpb = max(256 // (c // 8), 1)
+    expected = max(min(-(-m // rpb), 1024), 1)
+    assert ops._load_extension().bn_num_rblocks(m, c) == expected
+
+
+def test_bn_num_rblocks_rejects_unsupported_channels():
+    with pytest.raises(RuntimeError, match="C % 8 == 0"):
+        ops._load_extension().bn_num_rblocks(256, 4)
+
+
 @pytest.mark.parametrize("momentum,nesterov,wd", [
     (0.0, False, 0.0), (0.9, False, 5e-4), (0.9, True, 5e-4)])
 def test_fused_sgd(momentum, nesterov, wd):
