@@ -165,13 +165,67 @@ def fused_adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2,
         param.addcdiv_(exp_avg, denom, value=-lr / bias1)
 
 
+def fused_sgd_master_step(param_lp, grad_lp, master, momentum_buf, lr,
+                          momentum, weight_decay, dampening, nesterov):
+    """Flat-bucket SGD update of a bf16/fp16 bucket with fp32 master
+    weights (single fused pass on GPU).
+
+    ``master`` (fp32) is the weight the update integrates;
+    ``momentum_buf`` is fp32; ``grad_lp`` is read-only; ``param_lp`` is
+    only written, with ``master`` rounded to its dtype.
+    """
+    ext = _require_ext(param_lp)
+    if ext is not None:
+        ext.fused_sgd_mw(_flat(param_lp), _flat(grad_lp), _flat(master),
+                         _flat(momentum_buf) if momentum_buf is not None
+                         else torch.empty(0, device=master.device,
+                                          dtype=master.dtype),
+                         float(lr), float(momentum), float(weight_decay),
+                         float(dampening), bool(nesterov))
+    else:
+        fused_sgd_step(master, grad_lp.float(), momentum_buf, lr, momentum,
+                       weight_decay, dampening, nesterov)
+        param_lp.copy_(master)
+
+
+def fused_adamw_master_step(param_lp, grad_lp, master, exp_avg, exp_avg_sq,
+                            lr, beta1, beta2, eps, weight_decay, step,
+                            adam_mode):
+    """Flat-bucket Adam/AdamW update of a bf16/fp16 bucket with fp32
+    master weights and fp32 moments (single fused pass on GPU); operands
+    as in :func:`fused_sgd_master_step`."""
+    ext = _require_ext(param_lp)
+    if ext is not None:
+        ext.fused_adamw_mw(_flat(param_lp), _flat(grad_lp), _flat(master),
+                           _flat(exp_avg), _flat(exp_avg_sq), float(lr),
+                           float(beta1), float(beta2), float(eps),
+                           float(weight_decay), int(step), bool(adam_mode))
+    else:
+        fused_adamw_step(master, grad_lp.float(), exp_avg, exp_avg_sq, lr,
+                         beta1, beta2, eps, weight_decay, step, adam_mode)
+        param_lp.copy_(master)
+
+
+def _precond_v(exp_avg_sq):
+    """The GPU preconditioner kernels take the second moment in fp32
+    (what the fused optimizers keep, with or without master weights).
+    A stock torch optimizer on a bf16/fp16 model keeps it in the
+    parameter dtype: widen that copy for the kernel."""
+    if exp_avg_sq.dtype != torch.float32:
+        return exp_avg_sq.float()
+    return exp_avg_sq
+
+
 def precond_sqsum(grad, exp_avg_sq, beta2, eps, step, out):
     """out += sum((grad / pinv)**2) with Adam preconditioner
-    pinv = sqrt(exp_avg_sq / (1 - beta2**step)) + eps  (fp64 accumulate)."""
+    pinv = sqrt(exp_avg_sq / (1 - beta2**step)) + eps  (fp64 accumulate).
+
+    ``grad`` may be bf16/fp16 with an fp32 ``exp_avg_sq`` (master-weight
+    buckets)."""
     ext = _require_ext(grad)
     if ext is not None:
-        ext.precond_sqsum(_flat(grad), _flat(exp_avg_sq), float(beta2),
-                          float(eps), int(step), out)
+        ext.precond_sqsum(_flat(grad), _flat(_precond_v(exp_avg_sq)),
+                          float(beta2), float(eps), int(step), out)
     else:
         corr = 1.0 - beta2 ** step
         pinv = (_flat(exp_avg_sq).double() / corr).sqrt().add_(eps)

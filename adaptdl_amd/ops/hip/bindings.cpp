@@ -92,12 +92,20 @@ void sqsum_avg(torch::Tensor cur, torch::Tensor prev, torch::Tensor out) {
 
 void precond_sqsum(torch::Tensor g, torch::Tensor v, double beta2,
                    double eps, long step, torch::Tensor out) {
-    check_f32(g, "g"); check_f32(v, "v"); check_out(out);
+    // g may be a bf16/fp16 bucket with an fp32 v (master-weight Adam).
+    const StatDtype gd = check_stat_in(g, "g");
+    check_f32(v, "v"); check_out(out);
     TORCH_CHECK(g.numel() == v.numel(), "g/v size mismatch");
     long n = g.numel();
     if (n == 0) return;
     double corr = 1.0 - std::pow(beta2, (double)step);
     float inv_corr_sqrt = (float)(1.0 / std::sqrt(corr));
+    if (gd != STAT_F32) {
+        launch_precond_sqsum_mw(gd, g.data_ptr(), v.data_ptr<float>(), n,
+                                inv_corr_sqrt, (float)eps,
+                                out.data_ptr<double>(), stream());
+        return;
+    }
     launch_precond_sqsum(g.data_ptr<float>(), v.data_ptr<float>(), n,
                          inv_corr_sqrt, (float)eps, out.data_ptr<double>(),
                          stream());
@@ -108,12 +116,19 @@ void precond_sqsum_dev(torch::Tensor g, torch::Tensor v, torch::Tensor pc,
     // hipGraph-capturable variant: bias-correction scalars pc =
     // {inv_corr_sqrt, eps, use_precond, unused} live in device memory
     // (updated by the eager fused-Adam step between replays).
-    check_f32(g, "g"); check_f32(v, "v"); check_out(out);
+    const StatDtype gd = check_stat_in(g, "g");
+    check_f32(v, "v"); check_out(out);
     check_f32(pc, "pc");
     TORCH_CHECK(g.numel() == v.numel(), "g/v size mismatch");
     TORCH_CHECK(pc.numel() >= 3, "pc must hold >= 3 scalars");
     long n = g.numel();
     if (n == 0) return;
+    if (gd != STAT_F32) {
+        launch_precond_sqsum_dev_mw(gd, g.data_ptr(), v.data_ptr<float>(),
+                                    n, pc.data_ptr<float>(),
+                                    out.data_ptr<double>(), stream());
+        return;
+    }
     launch_precond_sqsum_dev(g.data_ptr<float>(), v.data_ptr<float>(), n,
                              pc.data_ptr<float>(), out.data_ptr<double>(),
                              stream());
@@ -150,6 +165,59 @@ void fused_adamw(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                        (float)lr, (float)beta1, (float)beta2, (float)eps,
                        (float)weight_decay, bias1, bias2, (int)adam_mode,
                        stream());
+}
+
+// Master-weight forms: p (write-only) and g share one 16-bit dtype; the
+// master w and the optimizer state are fp32.
+StatDtype check_lp_pair(const torch::Tensor& p, const torch::Tensor& g) {
+    const StatDtype dtype = check_stat_in(p, "p");
+    check_stat_in(g, "g");
+    TORCH_CHECK(dtype != STAT_F32,
+                "p must be bfloat16 or float16 (float32 parameters take "
+                "fused_sgd / fused_adamw)");
+    TORCH_CHECK(g.scalar_type() == p.scalar_type(), "p/g dtype mismatch");
+    TORCH_CHECK(g.numel() == p.numel(), "p/g size mismatch");
+    return dtype;
+}
+
+void check_f32_n(const torch::Tensor& t, long n, const char* name) {
+    check_f32(t, name);
+    TORCH_CHECK(t.numel() == n, name, " size mismatch");
+}
+
+void fused_sgd_mw(torch::Tensor p, torch::Tensor g, torch::Tensor w,
+                  torch::Tensor m, double lr, double momentum,
+                  double weight_decay, double dampening, bool nesterov) {
+    const StatDtype dtype = check_lp_pair(p, g);
+    long n = p.numel();
+    check_f32_n(w, n, "master");
+    bool has_m = momentum != 0.0;
+    if (has_m) check_f32_n(m, n, "momentum_buf");
+    if (n == 0) return;
+    launch_fused_sgd_mw(dtype, p.data_ptr(), g.data_ptr(),
+                        w.data_ptr<float>(),
+                        has_m ? m.data_ptr<float>() : nullptr, n, (float)lr,
+                        (float)momentum, (float)weight_decay,
+                        (float)dampening, (int)nesterov, (int)has_m,
+                        stream());
+}
+
+void fused_adamw_mw(torch::Tensor p, torch::Tensor g, torch::Tensor w,
+                    torch::Tensor m, torch::Tensor v, double lr,
+                    double beta1, double beta2, double eps,
+                    double weight_decay, long step, bool adam_mode) {
+    const StatDtype dtype = check_lp_pair(p, g);
+    long n = p.numel();
+    check_f32_n(w, n, "master");
+    check_f32_n(m, n, "m"); check_f32_n(v, n, "v");
+    if (n == 0) return;
+    float bias1 = (float)(1.0 - std::pow(beta1, (double)step));
+    float bias2 = (float)(1.0 - std::pow(beta2, (double)step));
+    launch_fused_adamw_mw(dtype, p.data_ptr(), g.data_ptr(),
+                          w.data_ptr<float>(), m.data_ptr<float>(),
+                          v.data_ptr<float>(), n, (float)lr, (float)beta1,
+                          (float)beta2, (float)eps, (float)weight_decay,
+                          bias1, bias2, (int)adam_mode, stream());
 }
 
 // ---- fused NHWC BatchNorm(+ReLU) -------------------------------------
@@ -455,6 +523,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
             "precond_sqsum with device-resident scalars (graph-safe)");
     mod.def("fused_sgd", &fused_sgd, "fused flat-bucket SGD step");
     mod.def("fused_adamw", &fused_adamw, "fused flat-bucket Adam(W) step");
+    mod.def("fused_sgd_mw", &fused_sgd_mw,
+            "fused SGD step, bf16/fp16 bucket with fp32 master weights");
+    mod.def("fused_adamw_mw", &fused_adamw_mw,
+            "fused Adam(W) step, bf16/fp16 bucket with fp32 master weights");
     mod.def("bn_fwd", &bn_fwd, "fused NHWC bf16 BatchNorm(+ReLU) forward");
     mod.def("bn_bwd", &bn_bwd, "fused NHWC bf16 BatchNorm(+ReLU) backward");
     mod.def("bn_num_rblocks", &bn_ws_rows,

@@ -26,6 +26,10 @@
 //   per wave -> one global fp64 atomicAdd per block (Guideline 12)
 // - elementwise writes (scale / prev-copy) fused into the same pass so
 //   gradient bytes are touched exactly once more than strictly necessary
+// - master-weight kernels (*_mw_bf16 / *_mw_fp16: 16-bit gradient and
+//   parameter, fp32 master and optimizer state) use sibling traversals
+//   with the same head / 16-byte body / tail shape, pairing one 16-bit
+//   vector with two fp32 vectors per lane
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -302,6 +306,90 @@ STAT_KERNEL k_precond_sqsum_dev(const float* __restrict__ g,
         stat_pass<F32>(g, n, SqSum{}, out);
 }
 
+// ---- preconditioned statistic on master-weight buckets ---------------
+// PrecondSqSum with g in the bucket dtype (bf16/fp16) and v in fp32 (the
+// fused master-weight Adam keeps its moments in fp32).  A sibling of
+// stat_pass rather than a second-operand trait on it, so the single-
+// dtype instantiations above stay exactly the kernels they were.  One
+// 16-byte vector of g (8 elements) pairs with two 16-byte vectors of v;
+// the head aligns g, and v + head must then be 16-byte aligned as well
+// (true whenever both carry the same element offset), else the launch
+// takes the scalar loop — a grid-uniform branch on kernel arguments.
+template <class T>
+__device__ __forceinline__ void precond_pass_mw(
+        const typename T::elem* __restrict__ g, const float* __restrict__ v,
+        long n, const PrecondSqSum f, double* __restrict__ out) {
+    typedef typename T::elem E;
+    typedef typename T::vec V;
+    typedef F32::vec V4;
+    constexpr int W = T::W;
+    static_assert(W == 2 * F32::W, "one g vector pairs with two v vectors");
+    double acc = 0.0;
+    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    const long stride = (long)gridDim.x * BLOCK;
+
+    auto scalar = [&](long j) {
+        float pinv = sqrtf(v[j]) * f.ics + f.eps;
+        double q = (double)(T::to_f(g[j]) / pinv);
+        acc += q * q;
+    };
+
+    long head = (16 - ((size_t)g & 15)) / sizeof(E) & (W - 1);
+    if (((size_t)(v + head) & 15) != 0) head = n;
+    if (head > n) head = n;
+    for (long j = i; j < head; j += stride) scalar(j);
+
+    const long nv = (n - head) / W;
+    for (long j = i; j < nv; j += stride) {
+        const V vg = ((const V*)(g + head))[j];
+        const V4 v0 = ((const V4*)(v + head))[2 * j];
+        const V4 v1 = ((const V4*)(v + head))[2 * j + 1];
+        #pragma unroll
+        for (int k = 0; k < W; ++k) {
+            float vk = k < F32::W ? v0[k & 3] : v1[k & 3];
+            float pinv = sqrtf(vk) * f.ics + f.eps;
+            E eg = vg[k];
+            double q = (double)(T::to_f(eg) / pinv);
+            acc += q * q;
+        }
+    }
+
+    for (long j = head + nv * W + i; j < n; j += stride) scalar(j);
+    block_reduce_atomic(acc, out);
+}
+
+STAT_KERNEL k_precond_sqsum_mw_bf16(const unsigned short* __restrict__ g,
+                                    const float* __restrict__ v, long n,
+                                    float inv_corr_sqrt, float eps,
+                                    double* __restrict__ out) {
+    precond_pass_mw<BF16>(g, v, n, PrecondSqSum{inv_corr_sqrt, eps}, out);
+}
+STAT_KERNEL k_precond_sqsum_mw_fp16(const unsigned short* __restrict__ g,
+                                    const float* __restrict__ v, long n,
+                                    float inv_corr_sqrt, float eps,
+                                    double* __restrict__ out) {
+    precond_pass_mw<FP16>(g, v, n, PrecondSqSum{inv_corr_sqrt, eps}, out);
+}
+
+// Device-scalar forms (see k_precond_sqsum_dev): plain sqsum of g when
+// use_precond == 0.
+STAT_KERNEL k_precond_sqsum_dev_mw_bf16(
+        const unsigned short* __restrict__ g, const float* __restrict__ v,
+        long n, const float* __restrict__ pc, double* __restrict__ out) {
+    if (pc[2] != 0.f)
+        precond_pass_mw<BF16>(g, v, n, PrecondSqSum{pc[0], pc[1]}, out);
+    else
+        stat_pass<BF16>(g, n, SqSum{}, out);
+}
+STAT_KERNEL k_precond_sqsum_dev_mw_fp16(
+        const unsigned short* __restrict__ g, const float* __restrict__ v,
+        long n, const float* __restrict__ pc, double* __restrict__ out) {
+    if (pc[2] != 0.f)
+        precond_pass_mw<FP16>(g, v, n, PrecondSqSum{pc[0], pc[1]}, out);
+    else
+        stat_pass<FP16>(g, n, SqSum{}, out);
+}
+
 // ---- fused flat-bucket optimizers -----------------------------------
 
 // SGD with momentum on one flat bucket (param/grad/momentum share layout).
@@ -347,6 +435,188 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_fused_adamw(
         float denom = sqrtf(vj) * inv_bias2_sqrt + eps;
         p[j] = fmaf(-step_size, mj / denom, pj);
     }
+}
+
+// ---- fused optimizers with fp32 master weights (bf16/fp16 buckets) ---
+// The bucket's parameters and gradients are bf16/fp16; the weight the
+// optimizer integrates is an fp32 master, and the state is fp32.  One
+// pass reads g (low precision), the master and the state, does the
+// update in fp32 with the math of k_fused_sgd / k_fused_adamw, and
+// writes master, state and p = T::from_f(master) (RNE).  p is write-only:
+// the master is the only source of the weight.
+//
+// update<S>(g, w, s0, s1) of a functor rewrites the master w and its S
+// fp32 state elements in place.
+
+template <bool HAS_MOMENTUM>
+struct SgdUpdate {
+    static constexpr int states = HAS_MOMENTUM ? 1 : 0;
+    float lr, momentum, weight_decay, dampening;
+    int nesterov;
+    __device__ __forceinline__ void update(float dp, float& w, float& m,
+                                           float&) const {
+        if (weight_decay != 0.f) dp = fmaf(weight_decay, w, dp);
+        if (HAS_MOMENTUM) {
+            m = fmaf(momentum, m, (1.f - dampening) * dp);
+            dp = nesterov ? fmaf(momentum, m, dp) : m;
+        }
+        w = fmaf(-lr, dp, w);
+    }
+};
+
+struct AdamUpdate {
+    static constexpr int states = 2;
+    float lr, beta1, beta2, eps, weight_decay, step_size, inv_bias2_sqrt;
+    int adam_mode;
+    __device__ __forceinline__ void update(float g, float& w, float& m,
+                                           float& v) const {
+        if (adam_mode && weight_decay != 0.f) g = fmaf(weight_decay, w, g);
+        else if (!adam_mode && weight_decay != 0.f)
+            w *= (1.f - lr * weight_decay);
+        m = fmaf(beta1, m, (1.f - beta1) * g);
+        v = fmaf(beta2, v, (1.f - beta2) * g * g);
+        float denom = sqrtf(v) * inv_bias2_sqrt + eps;
+        w = fmaf(-step_size, m / denom, w);
+    }
+};
+
+// The parameter is the STORED master rounded to 16 bits.  Left alone,
+// the compiler folds the update's last fma and the conversion into one
+// v_fma_mix{lo,hi}_f16, which rounds the exact sum once and so differs
+// from RNE(fp32 master) in the double-rounding cases.  Passing the
+// master through an empty asm keeps the fp32 rounding in between.
+__device__ __forceinline__ float as_stored(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+
+// Grid-stride pass of update functor F over n elements.  The low-
+// precision streams move one 16-byte vector (8 elements) per lane, each
+// fp32 stream two; scalar head until p is 16-byte aligned, scalar tail.
+// Every operand must be 16-byte aligned after the head (true whenever
+// all carry the same element offset into 16-byte-aligned buffers);
+// otherwise the whole launch takes the scalar loop — grid-uniform, as it
+// depends on kernel arguments only.  s0 / s1 are dereferenced only for
+// the first F::states of them.
+template <class T, class F>
+__device__ __forceinline__ void update_pass_mw(
+        typename T::elem* __restrict__ p,
+        const typename T::elem* __restrict__ g, float* __restrict__ w,
+        float* __restrict__ s0, float* __restrict__ s1, long n, const F f) {
+    typedef typename T::elem E;
+    typedef typename T::vec V;
+    typedef F32::vec V4;
+    constexpr int W = T::W, S = F::states;
+    static_assert(W == 2 * F32::W, "one 16-bit vector pairs with two fp32");
+    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    const long stride = (long)gridDim.x * BLOCK;
+
+    auto scalar = [&](long j) {
+        float wj = w[j], a = 0.f, b = 0.f;
+        if constexpr (S >= 1) a = s0[j];
+        if constexpr (S >= 2) b = s1[j];
+        f.update(T::to_f(g[j]), wj, a, b);
+        wj = as_stored(wj);
+        w[j] = wj;
+        if constexpr (S >= 1) s0[j] = a;
+        if constexpr (S >= 2) s1[j] = b;
+        p[j] = T::from_f(wj);
+    };
+
+    long head = (16 - ((size_t)p & 15)) / sizeof(E) & (W - 1);
+    size_t mis = (size_t)(g + head) | (size_t)(w + head);
+    if constexpr (S >= 1) mis |= (size_t)(s0 + head);
+    if constexpr (S >= 2) mis |= (size_t)(s1 + head);
+    if ((mis & 15) != 0) head = n;
+    if (head > n) head = n;
+    for (long j = i; j < head; j += stride) scalar(j);
+
+    const long nv = (n - head) / W;
+    for (long j = i; j < nv; j += stride) {
+        const V vg = ((const V*)(g + head))[j];
+        V4 vw[2], va[2] = {V4(), V4()}, vb[2] = {V4(), V4()};
+        #pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            vw[h] = ((const V4*)(w + head))[2 * j + h];
+            if constexpr (S >= 1) va[h] = ((const V4*)(s0 + head))[2 * j + h];
+            if constexpr (S >= 2) vb[h] = ((const V4*)(s1 + head))[2 * j + h];
+        }
+        V vp;
+        #pragma unroll
+        for (int k = 0; k < W; ++k) {
+            E eg = vg[k];
+            float wk = vw[k / 4][k % 4], a = va[k / 4][k % 4],
+                  b = vb[k / 4][k % 4];
+            f.update(T::to_f(eg), wk, a, b);
+            wk = as_stored(wk);
+            vw[k / 4][k % 4] = wk;
+            va[k / 4][k % 4] = a;
+            vb[k / 4][k % 4] = b;
+            vp[k] = T::from_f(wk);
+        }
+        #pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            ((V4*)(w + head))[2 * j + h] = vw[h];
+            if constexpr (S >= 1) ((V4*)(s0 + head))[2 * j + h] = va[h];
+            if constexpr (S >= 2) ((V4*)(s1 + head))[2 * j + h] = vb[h];
+        }
+        ((V*)(p + head))[j] = vp;
+    }
+
+    for (long j = head + nv * W + i; j < n; j += stride) scalar(j);
+}
+
+#define UPDATE_KERNEL extern "C" __global__ __launch_bounds__(BLOCK) void
+
+template <class T>
+__device__ __forceinline__ void fused_sgd_mw(
+        typename T::elem* p, const typename T::elem* g, float* w, float* m,
+        long n, float lr, float momentum, float weight_decay,
+        float dampening, int nesterov, int has_momentum) {
+    if (has_momentum)
+        update_pass_mw<T>(p, g, w, m, (float*)nullptr, n,
+                          SgdUpdate<true>{lr, momentum, weight_decay,
+                                          dampening, nesterov});
+    else
+        update_pass_mw<T>(p, g, w, (float*)nullptr, (float*)nullptr, n,
+                          SgdUpdate<false>{lr, momentum, weight_decay,
+                                           dampening, nesterov});
+}
+
+UPDATE_KERNEL k_fused_sgd_mw_bf16(
+        unsigned short* __restrict__ p, const unsigned short* __restrict__ g,
+        float* __restrict__ w, float* __restrict__ m, long n, float lr,
+        float momentum, float weight_decay, float dampening, int nesterov,
+        int has_momentum) {
+    fused_sgd_mw<BF16>(p, g, w, m, n, lr, momentum, weight_decay, dampening,
+                       nesterov, has_momentum);
+}
+UPDATE_KERNEL k_fused_sgd_mw_fp16(
+        unsigned short* __restrict__ p, const unsigned short* __restrict__ g,
+        float* __restrict__ w, float* __restrict__ m, long n, float lr,
+        float momentum, float weight_decay, float dampening, int nesterov,
+        int has_momentum) {
+    fused_sgd_mw<FP16>(p, g, w, m, n, lr, momentum, weight_decay, dampening,
+                       nesterov, has_momentum);
+}
+
+UPDATE_KERNEL k_fused_adamw_mw_bf16(
+        unsigned short* __restrict__ p, const unsigned short* __restrict__ g,
+        float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+        long n, float lr, float beta1, float beta2, float eps,
+        float weight_decay, float bias1, float bias2, int adam_mode) {
+    update_pass_mw<BF16>(p, g, w, m, v, n,
+                         AdamUpdate{lr, beta1, beta2, eps, weight_decay,
+                                    lr / bias1, rsqrtf(bias2), adam_mode});
+}
+UPDATE_KERNEL k_fused_adamw_mw_fp16(
+        unsigned short* __restrict__ p, const unsigned short* __restrict__ g,
+        float* __restrict__ w, float* __restrict__ m, float* __restrict__ v,
+        long n, float lr, float beta1, float beta2, float eps,
+        float weight_decay, float bias1, float bias2, int adam_mode) {
+    update_pass_mw<FP16>(p, g, w, m, v, n,
+                         AdamUpdate{lr, beta1, beta2, eps, weight_decay,
+                                    lr / bias1, rsqrtf(bias2), adam_mode});
 }
 
 // ---- host-side launchers (called from bindings.cpp, which is compiled
@@ -433,6 +703,80 @@ extern "C" void launch_precond_sqsum(const float* g, const float* v, long n,
 extern "C" void launch_precond_sqsum_dev(const float* g, const float* v, long n,
                               const float* pc, double* out, hipStream_t s) {
     launch(k_precond_sqsum_dev, n, s, g, v, n, pc, out);
+}
+
+// dtype names the 16-bit element type of g (STAT_BF16 / STAT_FP16; the
+// bindings send an all-fp32 call to the launchers above instead).
+extern "C" void launch_precond_sqsum_mw(StatDtype dtype, const void* g,
+                             const float* v, long n, float inv_corr_sqrt,
+                             float eps, double* out, hipStream_t s) {
+    switch (dtype) {
+    case STAT_BF16:
+        launch(k_precond_sqsum_mw_bf16, n, s, (const u16*)g, v, n,
+               inv_corr_sqrt, eps, out);
+        break;
+    case STAT_FP16:
+        launch(k_precond_sqsum_mw_fp16, n, s, (const u16*)g, v, n,
+               inv_corr_sqrt, eps, out);
+        break;
+    case STAT_F32: break;
+    }
+}
+
+extern "C" void launch_precond_sqsum_dev_mw(StatDtype dtype, const void* g,
+                                 const float* v, long n, const float* pc,
+                                 double* out, hipStream_t s) {
+    switch (dtype) {
+    case STAT_BF16:
+        launch(k_precond_sqsum_dev_mw_bf16, n, s, (const u16*)g, v, n, pc,
+               out);
+        break;
+    case STAT_FP16:
+        launch(k_precond_sqsum_dev_mw_fp16, n, s, (const u16*)g, v, n, pc,
+               out);
+        break;
+    case STAT_F32: break;
+    }
+}
+
+extern "C" void launch_fused_sgd_mw(StatDtype dtype, void* p, const void* g,
+                         float* w, float* m, long n, float lr,
+                         float momentum, float weight_decay,
+                         float dampening, int nesterov, int has_momentum,
+                         hipStream_t s) {
+    switch (dtype) {
+    case STAT_BF16:
+        launch(k_fused_sgd_mw_bf16, n, s, (u16*)p, (const u16*)g, w, m, n,
+               lr, momentum, weight_decay, dampening, nesterov,
+               has_momentum);
+        break;
+    case STAT_FP16:
+        launch(k_fused_sgd_mw_fp16, n, s, (u16*)p, (const u16*)g, w, m, n,
+               lr, momentum, weight_decay, dampening, nesterov,
+               has_momentum);
+        break;
+    case STAT_F32: break;
+    }
+}
+
+extern "C" void launch_fused_adamw_mw(StatDtype dtype, void* p, const void* g,
+                           float* w, float* m, float* v, long n, float lr,
+                           float beta1, float beta2, float eps,
+                           float weight_decay, float bias1, float bias2,
+                           int adam_mode, hipStream_t s) {
+    switch (dtype) {
+    case STAT_BF16:
+        launch(k_fused_adamw_mw_bf16, n, s, (u16*)p, (const u16*)g, w, m, v,
+               n, lr, beta1, beta2, eps, weight_decay, bias1, bias2,
+               adam_mode);
+        break;
+    case STAT_FP16:
+        launch(k_fused_adamw_mw_fp16, n, s, (u16*)p, (const u16*)g, w, m, v,
+               n, lr, beta1, beta2, eps, weight_decay, bias1, bias2,
+               adam_mode);
+        break;
+    case STAT_F32: break;
+    }
 }
 
 extern "C" void launch_fused_sgd(float* p, const float* g, float* m, long n, float lr,

@@ -39,6 +39,26 @@ void launch_fused_adamw(float* p, const float* g, float* m, float* v,
                         float eps, float weight_decay, float bias1,
                         float bias2, int adam_mode, hipStream_t s);
 
+// Master-weight forms: dtype (STAT_BF16 / STAT_FP16) is the element type
+// of the low-precision operands p and g; master w, optimizer state and
+// the Adam second moment v are fp32.
+void launch_precond_sqsum_mw(StatDtype dtype, const void* g,
+                             const float* v, long n, float inv_corr_sqrt,
+                             float eps, double* out, hipStream_t s);
+void launch_precond_sqsum_dev_mw(StatDtype dtype, const void* g,
+                                 const float* v, long n, const float* pc,
+                                 double* out, hipStream_t s);
+void launch_fused_sgd_mw(StatDtype dtype, void* p, const void* g,
+                         float* w, float* m, long n, float lr,
+                         float momentum, float weight_decay,
+                         float dampening, int nesterov, int has_momentum,
+                         hipStream_t s);
+void launch_fused_adamw_mw(StatDtype dtype, void* p, const void* g,
+                           float* w, float* m, float* v, long n, float lr,
+                           float beta1, float beta2, float eps,
+                           float weight_decay, float bias1, float bias2,
+                           int adam_mode, hipStream_t s);
+
 // ---- bn_kernels.hip (bf16 NHWC as raw unsigned short) ----------------
 
 // Rows of the stage-1 partials workspace (= stage-1 grid size) for M rows

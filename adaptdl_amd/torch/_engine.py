@@ -73,8 +73,8 @@ def _segment_view(seg, p):
 
 class Bucket(object):
     __slots__ = ["group_idx", "flat", "segments", "ready", "work", "prev",
-                 "param_flat", "sgd_momentum", "adam_state", "used",
-                 "prev_cycle_valid"]
+                 "param_flat", "master_flat", "sgd_momentum", "adam_state",
+                 "used", "prev_cycle_valid"]
 
     def __init__(self, group_idx, flat, segments):
         self.group_idx = group_idx
@@ -84,6 +84,7 @@ class Bucket(object):
         self.work = None          # in-flight all-reduce handle
         self.prev = None          # snapshot buffer (accumulation / GNS diff)
         self.param_flat = None    # fused-optimizer flat parameter buffer
+        self.master_flat = None   # fp32 master weights (bf16/fp16 bucket)
         self.sgd_momentum = None  # fused SGD momentum (FusedSGD)
         self.adam_state = None    # fused Adam moments (FusedAdam/W)
         self.used = False         # any gradient produced this cycle

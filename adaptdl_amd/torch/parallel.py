@@ -79,6 +79,11 @@ class AdaptiveDataParallel(torch.nn.Module):
         self.require_backward_grad_sync = True
 
         self._sync_module_states()
+        if hasattr(optimizer, "refresh_master_weights"):
+            # fp32 master weights (fused optimizers on bf16/fp16
+            # parameters) were taken from this replica's initial values
+            # at attach time; start them from the broadcast ones.
+            optimizer.refresh_master_weights()
 
         self._state = _AdaptiveDataParallelState(
             model, optimizer, lr_scheduler, mp_scaler, name)
