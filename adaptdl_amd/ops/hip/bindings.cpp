@@ -245,15 +245,29 @@ long bn_ws_rows(long m, long c) {
     return bn_num_rblocks(m, (int)c);
 }
 
-// y = [relu](bn(x)); fills sums(2C ws), save_mean/save_rstd/scale/shift(C).
+// Nullable M*C/8-byte ReLU bitmask (see kernels.h); empty tensor = none.
+unsigned char* bn_mask_ptr(const torch::Tensor& mask, long m, long c) {
+    if (!mask.defined() || mask.numel() == 0) return nullptr;
+    TORCH_CHECK(mask.is_cuda() && mask.scalar_type() == torch::kUInt8 &&
+                mask.is_contiguous() && mask.numel() == m * (c / 8),
+                "mask must be a contiguous uint8 GPU tensor of size ",
+                m * (c / 8));
+    return mask.data_ptr<unsigned char>();
+}
+
+// y = [relu](bn(x) [+ z]); fills save_mean/save_rstd/scale/shift(C).
+// mask (optional) receives the ReLU bitmask when relu and z are given;
+// num_batches_tracked (optional int64 scalar) is bumped in train mode.
 void bn_fwd(torch::Tensor x, torch::Tensor z, torch::Tensor y,
             torch::Tensor gamma, torch::Tensor beta,
             torch::Tensor running_mean, torch::Tensor running_var,
             double momentum, double eps, bool train, bool relu,
-            torch::Tensor ws, torch::Tensor sums,
+            torch::Tensor ws,
             torch::Tensor save_mean, torch::Tensor save_rstd,
-            torch::Tensor scale, torch::Tensor shift) {
+            torch::Tensor scale, torch::Tensor shift,
+            torch::Tensor mask, torch::Tensor num_batches_tracked) {
     check_bn_x(x, "x"); check_bn_x(y, "y");
+    TORCH_CHECK(y.sizes() == x.sizes(), "output shape mismatch");
     const unsigned short* zp = nullptr;
     if (z.defined() && z.numel() > 0) {
         check_bn_x(z, "z");
@@ -267,7 +281,6 @@ void bn_fwd(torch::Tensor x, torch::Tensor z, torch::Tensor y,
     check_vecf(gamma, c, "gamma"); check_vecf(beta, c, "beta");
     if (train)
         check_vecf(ws, 2 * c * bn_num_rblocks(m, (int)c), "ws");
-    check_vecf(sums, 2 * c, "sums");
     check_vecf(save_mean, c, "save_mean");
     check_vecf(save_rstd, c, "save_rstd");
     check_vecf(scale, c, "scale"); check_vecf(shift, c, "shift");
@@ -281,40 +294,64 @@ void bn_fwd(torch::Tensor x, torch::Tensor z, torch::Tensor y,
     } else {
         TORCH_CHECK(train, "eval-mode bn_fwd requires running statistics");
     }
+    unsigned char* mp = bn_mask_ptr(mask, m, c);
+    TORCH_CHECK(mp == nullptr || (relu && zp != nullptr),
+                "a ReLU mask is stored only with relu and a residual");
+    long long* nbt = nullptr;
+    if (num_batches_tracked.defined() && num_batches_tracked.numel() > 0) {
+        TORCH_CHECK(num_batches_tracked.is_cuda() &&
+                    num_batches_tracked.scalar_type() == torch::kInt64 &&
+                    num_batches_tracked.numel() == 1,
+                    "num_batches_tracked must be an int64 GPU scalar");
+        nbt = (long long*)num_batches_tracked.data_ptr<int64_t>();
+    }
     launch_bn_fwd((const unsigned short*)x.data_ptr(), zp,
                   (unsigned short*)y.data_ptr(), m, (int)c,
                   gamma.data_ptr<float>(), beta.data_ptr<float>(), rm, rv,
                   (float)momentum, (float)eps, (int)train, (int)relu,
                   train ? ws.data_ptr<float>() : nullptr,
-                  sums.data_ptr<float>(), save_mean.data_ptr<float>(),
+                  save_mean.data_ptr<float>(),
                   save_rstd.data_ptr<float>(), scale.data_ptr<float>(),
-                  shift.data_ptr<float>(), stream());
+                  shift.data_ptr<float>(), mp, nbt, stream());
 }
 
+// z: the forward's residual, or empty when `mask` (the forward's saved
+// ReLU bitmask) stands in for it; dz non-empty = also write dL/dz.
 void bn_bwd(torch::Tensor x, torch::Tensor z, torch::Tensor dy,
             torch::Tensor dx, torch::Tensor dz,
             torch::Tensor gamma, torch::Tensor save_mean,
             torch::Tensor save_rstd, torch::Tensor scale,
             torch::Tensor shift, bool train, bool relu, torch::Tensor ws,
-            torch::Tensor sums, torch::Tensor dgamma, torch::Tensor dbeta,
-            torch::Tensor pqr) {
+            torch::Tensor dgamma, torch::Tensor dbeta,
+            torch::Tensor pqr, torch::Tensor mask) {
     check_bn_x(x, "x"); check_bn_x(dy, "dy"); check_bn_x(dx, "dx");
-    const unsigned short* zp = nullptr;
-    unsigned short* dzp = nullptr;
-    if (z.defined() && z.numel() > 0) {
-        check_bn_x(z, "z"); check_bn_x(dz, "dz");
-        TORCH_CHECK(z.sizes() == x.sizes(), "residual shape mismatch");
-        zp = (const unsigned short*)z.data_ptr();
-        dzp = (unsigned short*)dz.data_ptr();
-    }
+    TORCH_CHECK(dy.sizes() == x.sizes() && dx.sizes() == x.sizes(),
+                "gradient shape mismatch");
     const long c = x.size(1);
     const long m = x.numel() / c;
+    TORCH_CHECK(c % 8 == 0 && c / 8 <= 256,
+                "bn_bwd requires C % 8 == 0 and C <= 2048, got C=", c);
+    const unsigned short* zp = nullptr;
+    unsigned short* dzp = nullptr;
+    const unsigned char* mp = bn_mask_ptr(mask, m, c);
+    if (z.defined() && z.numel() > 0) {
+        check_bn_x(z, "z");
+        TORCH_CHECK(z.sizes() == x.sizes(), "residual shape mismatch");
+        zp = (const unsigned short*)z.data_ptr();
+    }
+    if (dz.defined() && dz.numel() > 0) {
+        check_bn_x(dz, "dz");
+        TORCH_CHECK(dz.sizes() == x.sizes(), "residual shape mismatch");
+        TORCH_CHECK(zp != nullptr || mp != nullptr,
+                    "dz requires the residual or its saved ReLU mask");
+        dzp = (unsigned short*)dz.data_ptr();
+    }
+    TORCH_CHECK(mp == nullptr || relu, "a ReLU mask requires relu");
     check_vecf(gamma, c, "gamma");
     check_vecf(save_mean, c, "save_mean");
     check_vecf(save_rstd, c, "save_rstd");
     check_vecf(scale, c, "scale"); check_vecf(shift, c, "shift");
     check_vecf(ws, 2 * c * bn_num_rblocks(m, (int)c), "ws");
-    check_vecf(sums, 2 * c, "sums");
     check_vecf(dgamma, c, "dgamma"); check_vecf(dbeta, c, "dbeta");
     check_vecf(pqr, 3 * c, "pqr");
     launch_bn_bwd((const unsigned short*)x.data_ptr(), zp,
@@ -323,9 +360,9 @@ void bn_bwd(torch::Tensor x, torch::Tensor z, torch::Tensor dy,
                   gamma.data_ptr<float>(), save_mean.data_ptr<float>(),
                   save_rstd.data_ptr<float>(), scale.data_ptr<float>(),
                   shift.data_ptr<float>(), (int)train, (int)relu,
-                  ws.data_ptr<float>(), sums.data_ptr<float>(),
+                  ws.data_ptr<float>(),
                   dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                  pqr.data_ptr<float>(), stream());
+                  pqr.data_ptr<float>(), mp, stream());
 }
 
 // ---- custom MFMA conv 3x3 wrw ---------------------------------------

@@ -15,8 +15,13 @@
 //     cross-block atomics — v1 used one atomicAdd per (block, channel)
 //     and measured 432 us vs the 20 us bandwidth-bound apply pass, pure
 //     atomic serialization), then a parallel per-channel block reduce,
-//   - ReLU and its backward mask (recomputed from x — no extra stream)
-//     are folded in, so no separate threshold/clamp kernels run.
+//   - ReLU and its backward mask are folded in, so no separate
+//     threshold/clamp kernels run.  Without a residual the mask is
+//     recomputed from x (read anyway, no extra stream); with a residual
+//     the forward apply stores it as one bit per element so the backward
+//     does not re-read z,
+//   - the per-channel tail of each direction (workspace row sums +
+//     finalize math + the num_batches_tracked increment) is ONE kernel.
 //
 // Layout contract: x is NHWC ("channels_last") bf16 with C % 8 == 0 and
 // C/8 <= 256; per-channel parameters fp32.  M = N*H*W rows.
@@ -127,56 +132,101 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_fwd_reduce(
 }
 
 // ---------------------------------------------------------------------
-// Stage-2: one block per channel-statistic row; sums ws[row * nb .. +nb].
+// Stage-2 row sums for the tail kernels: block `ch` sums its two
+// workspace rows (ws[ch * nb ..] and ws[(c + ch) * nb ..]).  Strided
+// per-thread sum, wave shuffle tree, then the block's 4 wave partials in
+// index order.  Both totals are valid in thread 0 only.
+//
+// nb <= MAX_RBLOCKS = WS_TRIPS * BLOCK, so a thread owns at most WS_TRIPS
+// elements of each row: all 2 * WS_TRIPS loads issue up front (one memory
+// round trip instead of one per trip and row), then add in index order.
 // ---------------------------------------------------------------------
-extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_reduce_ws(
-        const float* __restrict__ ws, int nb, float* __restrict__ out) {
-    __shared__ float lds[BLOCK];
-    const float* row = ws + (size_t)blockIdx.x * nb;
-    float s = 0.f;
-    for (int i = threadIdx.x; i < nb; i += BLOCK) s += row[i];
-    // wave shuffle reduce, then LDS across the block's 4 waves
+#define WS_TRIPS (MAX_RBLOCKS / BLOCK)
+static_assert(WS_TRIPS * BLOCK == MAX_RBLOCKS, "row-sum trips cover a row");
+
+__device__ __forceinline__ void ws_row_pair_sum(
+        const float* __restrict__ ws, int nb, int c, int ch, float* lds,
+        float& t0, float& t1) {
+    const float* row0 = ws + (size_t)ch * nb;
+    const float* row1 = ws + (size_t)(c + ch) * nb;
+    float a[WS_TRIPS], b[WS_TRIPS];
     #pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1)
-        s += __shfl_down(s, off, WAVE);
+    for (int j = 0; j < WS_TRIPS; ++j) {
+        // clamped, so the loads are unconditional; the adds are guarded
+        const int i = min((int)threadIdx.x + j * BLOCK, nb - 1);
+        a[j] = row0[i];
+        b[j] = row1[i];
+    }
+    float s0 = 0.f, s1 = 0.f;
+    #pragma unroll
+    for (int j = 0; j < WS_TRIPS; ++j) {
+        if ((int)threadIdx.x + j * BLOCK < nb) { s0 += a[j]; s1 += b[j]; }
+    }
+    #pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+        s0 += __shfl_down(s0, off, WAVE);
+        s1 += __shfl_down(s1, off, WAVE);
+    }
     const int lane = threadIdx.x & (WAVE - 1);
     const int wid = threadIdx.x / WAVE;
-    if (lane == 0) lds[wid] = s;
+    if (lane == 0) {
+        lds[wid] = s0;
+        lds[BLOCK / WAVE + wid] = s1;
+    }
     __syncthreads();
+    t0 = 0.f; t1 = 0.f;
     if (threadIdx.x == 0) {
-        float t = 0.f;
         #pragma unroll
-        for (int i = 0; i < BLOCK / WAVE; ++i) t += lds[i];
-        out[blockIdx.x] = t;
+        for (int i = 0; i < BLOCK / WAVE; ++i) t0 += lds[i];
+        #pragma unroll
+        for (int i = 0; i < BLOCK / WAVE; ++i) t1 += lds[BLOCK / WAVE + i];
     }
 }
 
 // ---------------------------------------------------------------------
-// Forward finalize (C threads): statistics + affine fold + running stats.
+// Forward tail (C blocks): row sums, then one thread per channel does
+// statistics + affine fold + running stats.  Block 0 also bumps
+// num_batches_tracked when the module tracks it (nullable).
 // ---------------------------------------------------------------------
-extern "C" __global__ void k_bn_fwd_finalize(
-        const float* __restrict__ sums, long m, int c,
+extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_fwd_tail(
+        const float* __restrict__ ws, int nb, long m, int c,
         const float* __restrict__ gamma, const float* __restrict__ beta,
         float* __restrict__ running_mean, float* __restrict__ running_var,
         float momentum, float eps,
         float* __restrict__ save_mean, float* __restrict__ save_rstd,
-        float* __restrict__ scale, float* __restrict__ shift) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= c) return;
-    float inv_m = 1.0f / (float)m;
-    float mean = sums[i] * inv_m;
-    float var = sums[c + i] * inv_m - mean * mean;
-    var = var > 0.f ? var : 0.f;
-    float rstd = rsqrtf(var + eps);
-    save_mean[i] = mean;
-    save_rstd[i] = rstd;
-    float sc = gamma[i] * rstd;
-    scale[i] = sc;
-    shift[i] = beta[i] - mean * sc;
-    if (running_mean != nullptr) {
-        float unbiased = m > 1 ? var * (float)m / (float)(m - 1) : var;
-        running_mean[i] += momentum * (mean - running_mean[i]);
-        running_var[i] += momentum * (unbiased - running_var[i]);
+        float* __restrict__ scale, float* __restrict__ shift,
+        long long* __restrict__ num_batches_tracked) {
+    __shared__ float lds[2 * BLOCK / WAVE];
+    const int i = blockIdx.x;
+    // per-channel inputs first, so their latency hides under the row sums
+    const float g = gamma[i], b = beta[i];
+    const float rm = running_mean ? running_mean[i] : 0.f;
+    const float rv = running_mean ? running_var[i] : 0.f;
+    float sum, sumsq;
+    ws_row_pair_sum(ws, nb, c, i, lds, sum, sumsq);
+    // Rounding is pinned: no implicit contraction, and an explicit fmaf
+    // exactly where the former C-thread finalize kernel fused (shift and
+    // the running-statistics updates; the variance stays mul, mul, sub),
+    // so the statistics do not move with the compiler's choices here.
+    if (threadIdx.x == 0) {
+        #pragma clang fp contract(off)
+        float inv_m = 1.0f / (float)m;
+        float mean = sum * inv_m;
+        float var = sumsq * inv_m - mean * mean;
+        var = var > 0.f ? var : 0.f;
+        float rstd = rsqrtf(var + eps);
+        save_mean[i] = mean;
+        save_rstd[i] = rstd;
+        float sc = g * rstd;
+        scale[i] = sc;
+        shift[i] = fmaf(-mean, sc, b);
+        if (running_mean != nullptr) {
+            float unbiased = m > 1 ? var * (float)m / (float)(m - 1) : var;
+            running_mean[i] = fmaf(momentum, mean - rm, rm);
+            running_var[i] = fmaf(momentum, unbiased - rv, rv);
+        }
+        if (i == 0 && num_batches_tracked != nullptr)
+            *num_batches_tracked += 1;
     }
 }
 
@@ -207,7 +257,8 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_fwd_apply(
         const ushort_t* __restrict__ x, const ushort_t* __restrict__ z,
         ushort_t* __restrict__ y, long m, int c,
         const float* __restrict__ scale,
-        const float* __restrict__ shift, int relu) {
+        const float* __restrict__ shift, int relu,
+        unsigned char* __restrict__ mask) {
     const int slots = c / VEC;
     const int rpb = BLOCK / slots > 0 ? BLOCK / slots : 1;
     const int slot = threadIdx.x % slots;
@@ -228,14 +279,19 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_fwd_apply(
         in.f4 = *reinterpret_cast<const float4*>(xb + (size_t)row * c);
         if (zb)
             vz.f4 = *reinterpret_cast<const float4*>(zb + (size_t)row * c);
+        unsigned bits = 0;
         #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             float f = fmaf(b2f(in.u[k]), sc[k], sh[k]);
             if (zb) f += b2f(vz.u[k]);
+            if (f > 0.f) bits |= 1u << k;
             if (relu) f = f > 0.f ? f : 0.f;
             out.u[k] = f2b(f);
         }
         *reinterpret_cast<float4*>(yb + (size_t)row * c) = out.f4;
+        // rpb * slots == BLOCK whenever slots divides BLOCK, so a wave's
+        // 64 mask bytes are contiguous.
+        if (mask) mask[(size_t)row * slots + slot] = (unsigned char)bits;
     }
 }
 
@@ -249,7 +305,7 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_bwd_reduce(
         long m, int c, int nb, const float* __restrict__ mean,
         const float* __restrict__ rstd, const float* __restrict__ scale,
         const float* __restrict__ shift, int relu,
-        float* __restrict__ ws) {
+        const unsigned char* __restrict__ mask, float* __restrict__ ws) {
     const int slots = c / VEC;
     const int rpb = BLOCK / slots > 0 ? BLOCK / slots : 1;
     const int slot = threadIdx.x % slots;
@@ -278,11 +334,16 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_bwd_reduce(
                 vz.f4 = *reinterpret_cast<const float4*>(
                     zb + (size_t)row * c);
             vd.f4 = *reinterpret_cast<const float4*>(db + (size_t)row * c);
+            // saved forward ReLU mask (residual BNs): bit k = "kept"
+            unsigned bits = 0;
+            if (mask) bits = mask[(size_t)row * slots + slot];
             #pragma unroll
             for (int k = 0; k < VEC; ++k) {
                 float fx = b2f(vx.u[k]);
                 float g = b2f(vd.u[k]);
-                if (relu) {
+                if (mask) {
+                    if (!((bits >> k) & 1u)) g = 0.f;
+                } else if (relu) {
                     float pre = fmaf(fx, sc[k], sh[k]);
                     if (zb) pre += b2f(vz.u[k]);
                     if (pre <= 0.f) g = 0.f;
@@ -308,34 +369,40 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_bwd_reduce(
 }
 
 // ---------------------------------------------------------------------
-// Backward finalize (C threads): dgamma/dbeta + dx coefficients.
+// Backward tail (C blocks): row sums, then one thread per channel writes
+// dgamma/dbeta + dx coefficients.
 // dx = p * g - q * x + r  with g = masked dy:
 //   p = gamma * rstd
 //   q = p * (sum_gx / M) * rstd          (0 in eval mode)
 //   r = -p * (sum_g / M) + q * mean      (0 in eval mode)
 // ---------------------------------------------------------------------
-extern "C" __global__ void k_bn_bwd_finalize(
-        const float* __restrict__ sums, long m, int c,
+extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_bwd_tail(
+        const float* __restrict__ ws, int nb, long m, int c,
         const float* __restrict__ gamma, const float* __restrict__ mean,
         const float* __restrict__ rstd, int train,
         float* __restrict__ dgamma, float* __restrict__ dbeta,
         float* __restrict__ pqr) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= c) return;
-    float sum_g = sums[i];
-    float sum_gx = sums[c + i];
-    dbeta[i] = sum_g;
-    dgamma[i] = sum_gx;
-    float p = gamma[i] * rstd[i];
-    float q = 0.f, r = 0.f;
-    if (train) {
-        float inv_m = 1.0f / (float)m;
-        q = p * (sum_gx * inv_m) * rstd[i];
-        r = -p * (sum_g * inv_m) + q * mean[i];
+    __shared__ float lds[2 * BLOCK / WAVE];
+    const int i = blockIdx.x;
+    const float g = gamma[i], rs = rstd[i], mn = mean[i];
+    float sum_g, sum_gx;
+    ws_row_pair_sum(ws, nb, c, i, lds, sum_g, sum_gx);
+    // as in the forward tail: every product below rounds on its own
+    if (threadIdx.x == 0) {
+        #pragma clang fp contract(off)
+        dbeta[i] = sum_g;
+        dgamma[i] = sum_gx;
+        float p = g * rs;
+        float q = 0.f, r = 0.f;
+        if (train) {
+            float inv_m = 1.0f / (float)m;
+            q = p * (sum_gx * inv_m) * rs;
+            r = -p * (sum_g * inv_m) + q * mn;
+        }
+        pqr[i] = p;
+        pqr[c + i] = q;
+        pqr[2 * c + i] = r;
     }
-    pqr[i] = p;
-    pqr[c + i] = q;
-    pqr[2 * c + i] = r;
 }
 
 // ---------------------------------------------------------------------
@@ -348,7 +415,8 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_bwd_apply(
         ushort_t* __restrict__ dx, ushort_t* __restrict__ dz, long m,
         int c, const float* __restrict__ scale,
         const float* __restrict__ shift,
-        const float* __restrict__ pqr, int relu) {
+        const float* __restrict__ pqr, int relu,
+        const unsigned char* __restrict__ mask) {
     const int slots = c / VEC;
     const int rpb = BLOCK / slots > 0 ? BLOCK / slots : 1;
     const int slot = threadIdx.x % slots;
@@ -375,11 +443,15 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_bwd_apply(
         if (zb)
             vz.f4 = *reinterpret_cast<const float4*>(zb + (size_t)row * c);
         vd.f4 = *reinterpret_cast<const float4*>(db + (size_t)row * c);
+        unsigned bits = 0;
+        if (mask) bits = mask[(size_t)row * slots + slot];
         #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             float fx = b2f(vx.u[k]);
             float g = b2f(vd.u[k]);
-            if (relu) {
+            if (mask) {
+                if (!((bits >> k) & 1u)) g = 0.f;
+            } else if (relu) {
                 float pre = fmaf(fx, sc[k], sh[k]);
                 if (zb) pre += b2f(vz.u[k]);
                 if (pre <= 0.f) g = 0.f;
@@ -416,53 +488,55 @@ extern "C" long bn_num_rblocks(long m, int c) {
     return bn_grid(m, bn_rows_per_block(c), MAX_RBLOCKS);
 }
 
+// mask (nullable): M * C / 8 bytes, written only with relu and a residual.
+// num_batches_tracked (nullable): int64 scalar bumped by the forward tail.
 extern "C" void launch_bn_fwd(
         const ushort_t* x, const ushort_t* z, ushort_t* y, long m, int c,
         const float* gamma, const float* beta, float* running_mean,
         float* running_var, float momentum, float eps, int train, int relu,
-        float* ws, float* sums, float* save_mean, float* save_rstd,
-        float* scale, float* shift, hipStream_t s) {
+        float* ws, float* save_mean, float* save_rstd, float* scale,
+        float* shift, unsigned char* mask, long long* num_batches_tracked,
+        hipStream_t s) {
     const int rpb = bn_rows_per_block(c);
     if (train) {
         const unsigned nb = (unsigned)bn_num_rblocks(m, c);
         hipLaunchKernelGGL(k_bn_fwd_reduce, dim3(nb), dim3(BLOCK), 0, s,
                            x, m, c, (int)nb, ws);
-        hipLaunchKernelGGL(k_bn_reduce_ws, dim3(2 * c), dim3(BLOCK), 0, s,
-                           ws, (int)nb, sums);
-        hipLaunchKernelGGL(k_bn_fwd_finalize,
-                           dim3((c + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s,
-                           sums, m, c, gamma, beta, running_mean,
+        hipLaunchKernelGGL(k_bn_fwd_tail, dim3(c), dim3(BLOCK), 0, s,
+                           ws, (int)nb, m, c, gamma, beta, running_mean,
                            running_var, momentum, eps, save_mean, save_rstd,
-                           scale, shift);
+                           scale, shift, num_batches_tracked);
     } else {
         hipLaunchKernelGGL(k_bn_eval_finalize,
                            dim3((c + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s,
                            c, gamma, beta, running_mean, running_var, eps,
                            save_mean, save_rstd, scale, shift);
     }
+    if (!(relu && z)) mask = nullptr;
     hipLaunchKernelGGL(k_bn_fwd_apply, dim3(bn_grid(m, rpb, MAX_BLOCKS)),
                        dim3(BLOCK), 0, s, x, z, y, m, c, scale, shift,
-                       relu);
+                       relu, mask);
 }
 
+// With a mask (saved by the forward for relu + residual) z may be null:
+// the backward reads the mask byte instead of recomputing it from z.
 extern "C" void launch_bn_bwd(
         const ushort_t* x, const ushort_t* z, const ushort_t* dy,
         ushort_t* dx, ushort_t* dz, long m, int c,
         const float* gamma, const float* save_mean, const float* save_rstd,
         const float* scale, const float* shift, int train, int relu,
-        float* ws, float* sums, float* dgamma, float* dbeta, float* pqr,
-        hipStream_t s) {
+        float* ws, float* dgamma, float* dbeta, float* pqr,
+        const unsigned char* mask, hipStream_t s) {
     const int rpb = bn_rows_per_block(c);
     const unsigned nb = (unsigned)bn_num_rblocks(m, c);
+    if (!relu) mask = nullptr;
     hipLaunchKernelGGL(k_bn_bwd_reduce, dim3(nb), dim3(BLOCK), 0, s,
                        x, z, dy, m, c, (int)nb, save_mean, save_rstd,
-                       scale, shift, relu, ws);
-    hipLaunchKernelGGL(k_bn_reduce_ws, dim3(2 * c), dim3(BLOCK), 0, s,
-                       ws, (int)nb, sums);
-    hipLaunchKernelGGL(k_bn_bwd_finalize, dim3((c + BLOCK - 1) / BLOCK),
-                       dim3(BLOCK), 0, s, sums, m, c, gamma, save_mean,
-                       save_rstd, train, dgamma, dbeta, pqr);
+                       scale, shift, relu, mask, ws);
+    hipLaunchKernelGGL(k_bn_bwd_tail, dim3(c), dim3(BLOCK), 0, s,
+                       ws, (int)nb, m, c, gamma, save_mean, save_rstd,
+                       train, dgamma, dbeta, pqr);
     hipLaunchKernelGGL(k_bn_bwd_apply, dim3(bn_grid(m, rpb, MAX_BLOCKS)),
                        dim3(BLOCK), 0, s, x, z, dy, dx, dz, m, c, scale,
-                       shift, pqr, relu);
+                       shift, pqr, relu, mask);
 }

@@ -64,20 +64,25 @@ void launch_fused_adamw_mw(StatDtype dtype, void* p, const void* g,
 // Rows of the stage-1 partials workspace (= stage-1 grid size) for M rows
 // of C channels; ws holds 2 * C * bn_num_rblocks(M, C) floats.
 long bn_num_rblocks(long m, int c);
+// mask: nullable M*C/8-byte ReLU bitmask (relu + residual only), byte
+// [row * (C/8) + slot], bit k = channel slot*8+k kept.  The forward writes
+// it; the backward, given one, reads it instead of z (z may then be null).
+// num_batches_tracked: nullable int64 scalar the training forward bumps.
 void launch_bn_fwd(const unsigned short* x, const unsigned short* z,
                    unsigned short* y, long m, int c, const float* gamma,
                    const float* beta, float* running_mean,
                    float* running_var, float momentum, float eps,
-                   int train, int relu, float* ws, float* sums,
-                   float* save_mean, float* save_rstd, float* scale,
-                   float* shift, hipStream_t s);
+                   int train, int relu, float* ws, float* save_mean,
+                   float* save_rstd, float* scale, float* shift,
+                   unsigned char* mask, long long* num_batches_tracked,
+                   hipStream_t s);
 void launch_bn_bwd(const unsigned short* x, const unsigned short* z,
                    const unsigned short* dy, unsigned short* dx,
                    unsigned short* dz, long m, int c, const float* gamma,
                    const float* save_mean, const float* save_rstd,
                    const float* scale, const float* shift, int train,
-                   int relu, float* ws, float* sums, float* dgamma,
-                   float* dbeta, float* pqr, hipStream_t s);
+                   int relu, float* ws, float* dgamma, float* dbeta,
+                   float* pqr, const unsigned char* mask, hipStream_t s);
 
 // ---- conv_kernels.hip ------------------------------------------------
 

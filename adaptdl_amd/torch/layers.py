@@ -2,9 +2,10 @@
 
 FusedBatchNormAct2d is a drop-in BatchNorm2d(+ReLU) whose GPU path runs
 the hand-written CDNA4 NHWC kernels (adaptdl_amd/ops/hip/bn_kernels.hip)
-— one bandwidth-bound reduce + one apply pass per direction, with the
-ReLU and its backward mask folded in.  Motivation: on channels_last bf16
-ResNets MIOpen's NHWC spatial batchnorm is 56% of all kernel time
+— one bandwidth-bound reduce + one apply pass per direction plus one
+tiny per-channel tail kernel, with the ReLU and its backward mask folded
+in.  Motivation: on channels_last bf16 ResNets MIOpen's NHWC spatial
+batchnorm is 56% of all kernel time
 (profiles/bench_r02_channels_last_kernel_stats.csv).  On CPU (and for
 layouts the kernels do not cover) the same module falls back to the
 standard torch ops, so CPU tests exercise identical semantics.
@@ -34,7 +35,8 @@ def _hip_bn_ok(x):
 class _FusedBNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, z, weight, bias, running_mean, running_var,
-                training, momentum, eps, relu):
+                training, momentum, eps, relu, num_batches_tracked=None,
+                save_mask=False):
         ext = ops._load_extension()
         y = torch.empty_like(x)
         c = x.shape[1]
@@ -42,20 +44,29 @@ class _FusedBNFunction(torch.autograd.Function):
         opt = dict(dtype=torch.float32, device=x.device)
         ws = torch.empty(2 * c * ext.bn_num_rblocks(m, c), **opt) \
             if training else torch.empty(0, **opt)
-        sums = torch.empty(2 * c, **opt)
         save_mean = torch.empty(c, **opt)
         save_rstd = torch.empty(c, **opt)
         scale = torch.empty(c, **opt)
         shift = torch.empty(c, **opt)
         none = torch.empty(0, **opt)
         znone = torch.empty(0, dtype=x.dtype, device=x.device)
+        # relu + residual with a backward to follow (save_mask: grad mode
+        # is off in here, so the caller decides): the apply pass also
+        # stores the ReLU mask, one bit per element, and the backward
+        # reads that instead of the residual.
+        use_mask = bool(relu) and z is not None and bool(save_mask)
+        mask = torch.empty(m * (c // 8) if use_mask else 0,
+                           dtype=torch.uint8, device=x.device)
+        nbt = num_batches_tracked if num_batches_tracked is not None \
+            else torch.empty(0, dtype=torch.int64, device=x.device)
         ext.bn_fwd(x, z if z is not None else znone, y, weight, bias,
                    running_mean if running_mean is not None else none,
                    running_var if running_var is not None else none,
                    float(momentum), float(eps), bool(training), bool(relu),
-                   ws, sums, save_mean, save_rstd, scale, shift)
-        ctx.save_for_backward(x, z if z is not None else znone, weight,
-                              save_mean, save_rstd, scale, shift)
+                   ws, save_mean, save_rstd, scale, shift, mask, nbt)
+        ctx.save_for_backward(
+            x, z if z is not None and not use_mask else znone, mask,
+            weight, save_mean, save_rstd, scale, shift)
         ctx.bn_train = bool(training)
         ctx.bn_relu = bool(relu)
         ctx.bn_has_z = z is not None
@@ -64,7 +75,7 @@ class _FusedBNFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         ext = ops._load_extension()
-        x, z, weight, save_mean, save_rstd, scale, shift = \
+        x, z, mask, weight, save_mean, save_rstd, scale, shift = \
             ctx.saved_tensors
         dy = dy.contiguous(memory_format=torch.channels_last)
         dx = torch.empty_like(x)
@@ -74,15 +85,14 @@ class _FusedBNFunction(torch.autograd.Function):
         m = x.numel() // c
         opt = dict(dtype=torch.float32, device=x.device)
         ws = torch.empty(2 * c * ext.bn_num_rblocks(m, c), **opt)
-        sums = torch.empty(2 * c, **opt)
         dgamma = torch.empty(c, **opt)
         dbeta = torch.empty(c, **opt)
         pqr = torch.empty(3 * c, **opt)
         ext.bn_bwd(x, z, dy, dx, dz, weight, save_mean, save_rstd, scale,
-                   shift, ctx.bn_train, ctx.bn_relu, ws, sums, dgamma,
-                   dbeta, pqr)
+                   shift, ctx.bn_train, ctx.bn_relu, ws, dgamma, dbeta,
+                   pqr, mask)
         return (dx, dz if ctx.bn_has_z else None, dgamma, dbeta) + \
-            (None,) * 6
+            (None,) * 8
 
 
 class FusedBatchNormAct2d(nn.BatchNorm2d):
@@ -105,14 +115,17 @@ class FusedBatchNormAct2d(nn.BatchNorm2d):
                 (residual is None or
                  (residual.dtype == x.dtype and residual.is_contiguous(
                      memory_format=torch.channels_last))):
-            if self.training and self.track_running_stats and \
-                    self.num_batches_tracked is not None:
-                self.num_batches_tracked.add_(1)
+            # The forward tail kernel bumps the counter (no add_ launch).
+            nbt = self.num_batches_tracked if self.training and \
+                self.track_running_stats else None
             momentum = self.momentum if self.momentum is not None else 0.0
+            needs_bwd = torch.is_grad_enabled() and any(
+                t is not None and t.requires_grad
+                for t in (x, residual, self.weight, self.bias))
             return _FusedBNFunction.apply(
                 x, residual, self.weight, self.bias, self.running_mean,
                 self.running_var, use_batch_stats, momentum, self.eps,
-                self.relu)
+                self.relu, nbt, needs_bwd)
         y = super().forward(x)
         if residual is not None:
             y = y + residual
