@@ -28,7 +28,9 @@
 //   D[m][n]: lane l reg  r -> m = (l>>4)*4+r, n = l&15
 //
 // Constraints: 3x3, stride 1, pad 1, dilation 1, groups 1, NHWC bf16,
-// C % 64 == 0, K % 64 == 0, W in {8, 16, 32}, H % P == 0.
+// C % 64 == 0, K % 64 == 0, W in {8, 16, 32} (full-width chunks) or
+// {56, 28, 14, 7} (line padded to Wp), any H >= 2: a tail chunk with
+// H % P != 0 stages zero dy for its lines past H (conv3x3_wrw_params).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -522,7 +524,8 @@ extern "C" void launch_conv3x3_wrw(
 //     workspace: the contraction (9*C <= 1152) fits one block).
 // Dynamic LDS (up to ~128 KB) sized host-side.
 // Constraints: 3x3 s1 p1, NHWC bf16, W in {16, 32}, H % P == 0,
-// C % 32 == 0, C <= 128, K % KT == 0 (KT = 64 for C<=64 else 32).
+// C % 32 == 0, C <= 128 (C <= 96 at W = 32: the x window must fit the
+// 5 prefetch registers), K % KT == 0 (KT = 64 for C<=64 else 32).
 // =====================================================================
 
 struct MmRegs {
@@ -572,6 +575,17 @@ __device__ __forceinline__ void mm_write(
                 &x_s[(j * LP + 1 + ww) * CS + cg]) = r.v[it].u4;
         }
     }
+    // Refresh the zero pad columns (0 and W+1 of every line) on every
+    // staging: the y bounce store reuses this buffer and clobbers them.
+    const int zp = (P + 2) * (C / 8) * 2;
+    for (int i = t; i < zp; i += 512) {
+        const int j = i / ((C / 8) * 2);
+        const int rem = i % ((C / 8) * 2);
+        const int col = (rem & 1) ? (W + 1) : 0;
+        const int cg = (rem >> 1) * 8;
+        u32x4 z = {0u, 0u, 0u, 0u};
+        *reinterpret_cast<u32x4*>(&x_s[(j * LP + col) * CS + cg]) = z;
+    }
 }
 
 extern "C" __global__ __launch_bounds__(512, 2) void k_conv3x3_mm(
@@ -615,19 +629,7 @@ extern "C" __global__ __launch_bounds__(512, 2) void k_conv3x3_mm(
             *reinterpret_cast<u32x4*>(&w_lds[row * WS + cg]) = v.u4;
         }
     }
-    // ---- zero x pad columns of both buffers once ----
-    for (int b = 0; b < (dbuf ? 2 : 1); ++b) {
-        short* x_s = b ? x_s1 : x_s0;
-        for (int i = t; i < (P + 2) * (C / 8) * 2; i += 512) {
-            const int j = i / ((C / 8) * 2);
-            const int rem = i % ((C / 8) * 2);
-            const int col = (rem & 1) ? (W + 1) : 0;
-            const int cg = (rem >> 1) * 8;
-            u32x4 z = {0u, 0u, 0u, 0u};
-            *reinterpret_cast<u32x4*>(
-                &x_s[(j * LP + col) * CS + cg]) = z;
-        }
-    }
+    // (pad columns are zeroed inside mm_write on every staging)
 
     const int lines_per_img = H / P;
     const long chunks_total = (long)N * lines_per_img;
@@ -794,6 +796,9 @@ extern "C" int conv3x3_mm_supported(int H, int W, int C, int K) {
     if (W != 16 && W != 32) return 0;
     int P = (W == 32) ? 4 : 8;
     if (H % P) return 0;
+    // the x window must fit MmRegs (5 b128 pieces per thread): C=128
+    // at W=32 needs 6 and would leave the last window lines unstaged
+    if ((P + 2) * W * (C / 8) > 5 * 512) return 0;
     int KT = (C <= 64) ? 64 : 32;
     if (K % KT) return 0;
     return 1;
