@@ -31,6 +31,8 @@
 // C % 64 == 0, K % 64 == 0, W in {8, 16, 32} (full-width chunks) or
 // {56, 28, 14, 7} (line padded to Wp), any H >= 2: a tail chunk with
 // H % P != 0 stages zero dy for its lines past H (conv3x3_wrw_params).
+// H == W == 4 (any N >= 1) runs k_conv3x3_wrw_w4, which chunks by whole
+// images instead of lines (see its comment below).
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
@@ -271,6 +273,33 @@ __device__ __forceinline__ void wrw_mfma_phase(
     }
 }
 
+// Epilogue: write this wave's taus of the fp32 partial slab.
+__device__ __forceinline__ void wrw_store_slab(
+        float* __restrict__ slab, const f32x4 (&acc)[2][2][5], int C,
+        int kt, int ct, int wk, int wc, int wt2, int lane) {
+    #pragma unroll
+    for (int ti = 0; ti < 5; ++ti) {
+        if (wt2 && ti >= 4)
+            continue;
+        const int tau = (wt2 ? 5 : 0) + ti;
+        #pragma unroll
+        for (int mf = 0; mf < 2; ++mf) {
+            #pragma unroll
+            for (int nf = 0; nf < 2; ++nf) {
+                #pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int klocal = wk * 32 + mf * 16
+                        + ((lane >> 4) * 4 + r);
+                    const int clocal = wc * 32 + nf * 16
+                        + (lane & 15);
+                    slab[((size_t)(kt * 64 + klocal) * 9 + tau) * C
+                         + ct * 64 + clocal] = acc[mf][nf][ti][r];
+                }
+            }
+        }
+    }
+}
+
 // 8 waves: (wk, wc) tile quadrant x 2-wave tau split -- two waves per
 // SIMD interleave the alignbyte/window VALU work under each other's
 // MFMAs (phase probe: MFMA+VALU phase was ~150 us of the 218 us call
@@ -373,29 +402,251 @@ extern "C" __global__ __launch_bounds__(512, 2) void k_conv3x3_wrw(
     }
     #undef WRW_NH
 
-    // ---- epilogue: write the fp32 partial slab (this wave's taus) ---
-    float* slab = ws + (size_t)split * K * 9 * C;
+    wrw_store_slab(ws + (size_t)split * K * 9 * C, acc, C, kt, ct, wk, wc,
+                   wt2, lane);
+}
+
+// =====================================================================
+// 3x3 stride-1 weight gradient for 4x4 feature maps (ResNet layer4 on
+// CIFAR): k_conv3x3_wrw_w4.
+//
+// A 4x4 image is 16 pixels, half an MFMA K step, so the unit of work is
+// whole images: a chunk is W4_G = 8 images (128 pixels, flattened as
+// img*16 + h*4 + w) and one K step is the image pair (2kc, 2kc+1).  A
+// lane's 8 contraction elements (slot = lane>>4) are lines h0, h0+1 of
+// image 2kc + (slot>>1), h0 = (slot&1)*2.
+//
+//   - dy_t[k][pixel] is dense: a chunk's dy is one contiguous run of
+//     128 rows of K, staged exactly like the CP=128 shapes above
+//     (DY_STRIDE / DSWZ, one aligned b128 A fragment per (mf, kc)).
+//   - x_t[c][line][8]: every image line is ONE 16-byte padded line
+//     [0 0 x0 x1 x2 x3 0 0]; image g owns lines 5g+1 .. 5g+4 and the
+//     zero halo line 5g is shared with image g-1 (41 lines per chunk).
+//     For tap row dh the B fragment is padded lines h0+dh, h0+dh+1 of
+//     the lane's image: two aligned b128 reads.  Tap column dw selects
+//     shorts [1+dw .. 4+dw] of each line: dw=1 is dwords 1,2; dw=0/2
+//     are v_alignbyte by 2 of neighbouring dwords (three per line serve
+//     both).  A wave's tau half needs three consecutive lines per
+//     (nf, kc): 3 b128 reads feed 5 (or 4) taps.
+//   - Staging writes only the 4 real shorts of the 4 real lines of
+//     each image (zeros for images past N), so the pad columns and halo
+//     lines, zeroed once, stay zero: the x_t buffers hold nothing else.
+//   - Row stride 416 shorts (48 lines + 16 dwords, = 16 mod 64 banks)
+//     and an XOR of the LINE index by W4SWZ(row): the two slots of a
+//     b128 service group ({0-3,12-15,20-27}, ...) read lines 2 apart,
+//     so bit 0 of the line index separates rows 0-7 from 8-15; bits
+//     2,3 spread the 8 rows (8 apart) of one staging b32 write over the
+//     banks, with a half-wave writing lines h and h+2.  Modeled against
+//     the real lane groups: 1 cycle per b128 group and per b32
+//     half-wave.
+//
+// Work split, pipeline, slabs and reduce are those of k_conv3x3_wrw.
+// Constraints: H == W == 4, NHWC bf16, C % 64 == 0, K % 64 == 0, N >= 1.
+
+#define W4_G 8               // images per chunk (CP = 128)
+#define W4_XS 416            // shorts per x_t row
+#define W4_BUF (64 * DY_STRIDE + 64 * W4_XS)
+#define W4SWZ(row, line) \
+    ((line) ^ ((((row) >> 3) & 1) | ((((row) >> 4) & 3) << 2)))
+
+struct W4Regs {
+    V16 vdy[2];
+    V16 vx[2];
+};
+
+// x staging map: wave t>>6 stages image t>>6 of the chunk; the pixel
+// pair index pp puts lines h and h+2 into one half-wave (see above).
+#define W4_XH(t) (((((t) >> 3) & 1) * 2) + (((t) >> 5) & 1))
+#define W4_XW(t) ((((t) >> 4) & 1) * 2)
+
+__device__ __forceinline__ void w4_issue(
+        const ushort_t* __restrict__ x, const ushort_t* __restrict__ dy,
+        long q, long npix, int C, int K, int kt, int ct, int t,
+        W4Regs& r) {
+    const int c8 = (t & 7) * 8;
+    const long pd = q * (W4_G * 16) + (t >> 3) * 2;
+    if (pd < npix) {                 // npix is even: pd + 1 < npix too
+        const ushort_t* g = dy + (size_t)pd * K + (size_t)kt * 64 + c8;
+        r.vdy[0].u4 = *reinterpret_cast<const u32x4*>(g);
+        r.vdy[1].u4 = *reinterpret_cast<const u32x4*>(g + K);
+    } else {
+        r.vdy[0].u4 = u32x4{0u, 0u, 0u, 0u};
+        r.vdy[1].u4 = u32x4{0u, 0u, 0u, 0u};
+    }
+    const long px = q * (W4_G * 16) + (t >> 6) * 16 + W4_XH(t) * 4
+        + W4_XW(t);
+    if (px < npix) {
+        const ushort_t* g = x + (size_t)px * C + (size_t)ct * 64 + c8;
+        r.vx[0].u4 = *reinterpret_cast<const u32x4*>(g);
+        r.vx[1].u4 = *reinterpret_cast<const u32x4*>(g + C);
+    } else {
+        r.vx[0].u4 = u32x4{0u, 0u, 0u, 0u};
+        r.vx[1].u4 = u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+__device__ __forceinline__ void w4_write(
+        short* __restrict__ dy_t, short* __restrict__ x_t, int t,
+        W4Regs& r) {
+    const int c8 = (t & 7) * 8;
+    const int p = (t >> 3) * 2;
+    const int line = (t >> 6) * 5 + 1 + W4_XH(t);
+    const int col = 2 + W4_XW(t);
     #pragma unroll
-    for (int ti = 0; ti < 5; ++ti) {
-        if (wt2 && ti >= 4)
-            continue;
-        const int tau = (wt2 ? 5 : 0) + ti;
+    for (int j = 0; j < 8; ++j) {
+        const int row = c8 + j;
+        *reinterpret_cast<unsigned int*>(
+            &dy_t[row * DY_STRIDE + DSWZ(row, p)]) =
+            (unsigned int)(unsigned short)r.vdy[0].s[j]
+            | ((unsigned int)(unsigned short)r.vdy[1].s[j] << 16);
+        *reinterpret_cast<unsigned int*>(
+            &x_t[row * W4_XS + W4SWZ(row, line) * 8 + col]) =
+            (unsigned int)(unsigned short)r.vx[0].s[j]
+            | ((unsigned int)(unsigned short)r.vx[1].s[j] << 16);
+    }
+}
+
+// One chunk's MFMAs for this wave's tau half (WrwTaus<WT2>): tau group
+// g has tap row dh = WT2 + g and uses lines ln[g], ln[g + 1] of the
+// three padded lines h0 + WT2 .. h0 + WT2 + 2 read per (nf, kc).
+template <int WT2>
+__device__ __forceinline__ void w4_mfma_phase(
+        const short* __restrict__ dy_t, const short* __restrict__ x_t,
+        int wk, int wc, int row16, int slot, f32x4 (&acc)[2][2][5]) {
+    #pragma unroll
+    for (int kc = 0; kc < W4_G / 2; ++kc) {
+        bf16x8 afrag[2];
         #pragma unroll
         for (int mf = 0; mf < 2; ++mf) {
+            const int row = wk * 32 + mf * 16 + row16;
+            afrag[mf] = *reinterpret_cast<const bf16x8*>(
+                &dy_t[row * DY_STRIDE + DSWZ(row, kc * 32 + slot * 8)]);
+        }
+        const int lb = (2 * kc + (slot >> 1)) * 5 + (slot & 1) * 2 + WT2;
+        #pragma unroll
+        for (int nf = 0; nf < 2; ++nf) {
+            const int crow = wc * 32 + nf * 16 + row16;
+            // part[j][dw][0..1]: shorts [1+dw .. 4+dw] of line j
+            unsigned int part[3][3][2];
             #pragma unroll
-            for (int nf = 0; nf < 2; ++nf) {
+            for (int j = 0; j < 3; ++j) {
+                V16 ln;
+                ln.u4 = *reinterpret_cast<const u32x4*>(
+                    &x_t[crow * W4_XS + W4SWZ(crow, lb + j) * 8]);
+                const unsigned int mid =
+                    __builtin_amdgcn_alignbyte(ln.u[2], ln.u[1], 2);
+                part[j][0][0] =
+                    __builtin_amdgcn_alignbyte(ln.u[1], ln.u[0], 2);
+                part[j][0][1] = mid;
+                part[j][1][0] = ln.u[1];
+                part[j][1][1] = ln.u[2];
+                part[j][2][0] = mid;
+                part[j][2][1] =
+                    __builtin_amdgcn_alignbyte(ln.u[3], ln.u[2], 2);
+            }
+            int tj = 0;
+            #pragma unroll
+            for (int g = 0; g < 2; ++g) {
                 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int klocal = wk * 32 + mf * 16
-                        + ((lane >> 4) * 4 + r);
-                    const int clocal = wc * 32 + nf * 16
-                        + (lane & 15);
-                    slab[((size_t)(kt * 64 + klocal) * 9 + tau) * C
-                         + ct * 64 + clocal] = acc[mf][nf][ti][r];
+                for (int dw = 0; dw < 3; ++dw) {
+                    // WrwTaus<WT2>: taus 0..4 or 5..8
+                    if (WT2 ? (g == 0 && dw < 2) : (g == 1 && dw == 2))
+                        continue;
+                    const u32x4 frag = {part[g][dw][0], part[g][dw][1],
+                                        part[g + 1][dw][0],
+                                        part[g + 1][dw][1]};
+                    const bf16x8 bfrag =
+                        *reinterpret_cast<const bf16x8*>(&frag);
+                    #pragma unroll
+                    for (int mf = 0; mf < 2; ++mf)
+                        acc[mf][nf][tj] =
+                            __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                                afrag[mf], bfrag, acc[mf][nf][tj],
+                                0, 0, 0);
+                    ++tj;
                 }
             }
         }
     }
+}
+
+extern "C" __global__ __launch_bounds__(512, 2) void k_conv3x3_wrw_w4(
+        const ushort_t* __restrict__ x, const ushort_t* __restrict__ dy,
+        float* __restrict__ ws, int N, int C, int K, int nsplit) {
+    __shared__ short lds[2 * W4_BUF];
+
+    const int nc = C / 64;
+    const int tile = blockIdx.x / nsplit;
+    const int split = blockIdx.x % nsplit;
+    const int kt = tile / nc;
+    const int ct = tile % nc;
+
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wid = t >> 6;
+    const int wk = wid >> 2;
+    const int wc = (wid >> 1) & 1;
+    const int wt2 = wid & 1;         // tau half: 0 -> taus 0..4, 1 -> 5..8
+    const int row16 = lane & 15;
+    const int slot = lane >> 4;
+
+    f32x4 acc[2][2][5];
+    #pragma unroll
+    for (int mf = 0; mf < 2; ++mf)
+        #pragma unroll
+        for (int nf = 0; nf < 2; ++nf)
+            #pragma unroll
+            for (int ti = 0; ti < 5; ++ti)
+                #pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    acc[mf][nf][ti][r] = 0.f;
+
+    const long npix = (long)N * 16;
+    const long chunks_total = (N + W4_G - 1) / W4_G;
+
+    // Zero BOTH x_t buffers once: halo lines and pad columns are never
+    // written again, and nothing else ever lives in these buffers.
+    for (int b = 0; b < 2; ++b) {
+        u32x4* xz = reinterpret_cast<u32x4*>(
+            lds + b * W4_BUF + 64 * DY_STRIDE);
+        for (int i = t; i < 64 * W4_XS / 8; i += 512)
+            xz[i] = u32x4{0u, 0u, 0u, 0u};
+    }
+    __syncthreads();
+
+    W4Regs regs;
+    // Prologue: stage chunk 0 into buffer 0, issue chunk 1's loads.
+    if (split < chunks_total) {
+        w4_issue(x, dy, split, npix, C, K, kt, ct, t, regs);
+        w4_write(lds, lds + 64 * DY_STRIDE, t, regs);
+    }
+    __syncthreads();
+    if (split + nsplit < chunks_total)
+        w4_issue(x, dy, split + nsplit, npix, C, K, kt, ct, t, regs);
+
+    int cur = 0;
+    for (long q = split; q < chunks_total; q += nsplit, cur ^= 1) {
+        const short* dy_t = lds + cur * W4_BUF;
+        const short* x_t = dy_t + 64 * DY_STRIDE;
+
+        if (wt2 == 0)
+            w4_mfma_phase<0>(dy_t, x_t, wk, wc, row16, slot, acc);
+        else
+            w4_mfma_phase<1>(dy_t, x_t, wk, wc, row16, slot, acc);
+
+        // ---- stage chunk q+1 into the other buffer; issue q+2 ----
+        if (q + nsplit < chunks_total) {
+            short* ndy = lds + (cur ^ 1) * W4_BUF;
+            w4_write(ndy, ndy + 64 * DY_STRIDE, t, regs);
+            if (q + 2 * nsplit < chunks_total)
+                w4_issue(x, dy, q + 2 * nsplit, npix, C, K, kt, ct, t,
+                         regs);
+        }
+        __syncthreads();
+    }
+
+    wrw_store_slab(ws + (size_t)split * K * 9 * C, acc, C, kt, ct, wk, wc,
+                   wt2, lane);
 }
 
 // dW[i] = sum_s ws[s * n + i].  Hierarchical: each block sums a
@@ -469,6 +720,7 @@ extern "C" int conv3x3_wrw_params(int H, int W, int* P, int* Wp) {
 
 extern "C" int conv3x3_wrw_supported(int H, int W, int C, int K) {
     if (C % 64 || K % 64) return 0;
+    if (H == 4 && W == 4) return 1;   // k_conv3x3_wrw_w4
     int P, Wp;
     return conv3x3_wrw_params(H, W, &P, &Wp);
 }
@@ -477,6 +729,8 @@ extern "C" int conv3x3_wrw_nsplit(int N, int H, int W, int C, int K) {
     int P = 8, Wp = 8;
     conv3x3_wrw_params(H, W, &P, &Wp);
     long chunks = (long)N * ((H + P - 1) / P);
+    if (H == 4 && W == 4)             // chunks of W4_G whole images
+        chunks = (N + W4_G - 1) / W4_G;
     int tiles = (K / 64) * (C / 64);
     long target = 256 / tiles;  // one residency round (1 block/CU at 98 KB LDS)
     if (target < 1) target = 1;
@@ -491,8 +745,12 @@ extern "C" void launch_conv3x3_wrw(
     conv3x3_wrw_params(H, W, &P, &Wp);
     const int nsplit = conv3x3_wrw_nsplit(N, H, W, C, K);
     const int tiles = (K / 64) * (C / 64);
-    hipLaunchKernelGGL(k_conv3x3_wrw, dim3(tiles * nsplit), dim3(512), 0,
-                       s, x, dy, ws, N, H, W, Wp, C, K, P, nsplit);
+    if (H == 4 && W == 4)
+        hipLaunchKernelGGL(k_conv3x3_wrw_w4, dim3(tiles * nsplit),
+                           dim3(512), 0, s, x, dy, ws, N, C, K, nsplit);
+    else
+        hipLaunchKernelGGL(k_conv3x3_wrw, dim3(tiles * nsplit), dim3(512),
+                           0, s, x, dy, ws, N, H, W, Wp, C, K, P, nsplit);
     const long n = (long)K * 9 * C;
     // 16-slab groups: enough blocks to fill the chip (the 64-slab
     // version ran 144 blocks on layer1 and measured 5x off bandwidth).

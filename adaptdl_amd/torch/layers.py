@@ -299,6 +299,9 @@ class _S2Conv1x1Function(torch.autograd.Function):
         return dx, dw
 
 
+_WRW_W4_DEFAULT = "1"   # set by measurement, see FusedConv2d._wrw_ok
+
+
 class FusedConv2d(nn.Conv2d):
     """Conv2d whose 3x3/s1 weight gradient runs the MFMA wrw kernel."""
 
@@ -312,6 +315,13 @@ class FusedConv2d(nn.Conv2d):
             return False
         ext = ops._load_extension()
         n, c, h, w = x.shape
+        # 4x4 maps (layer4 on CIFAR) run k_conv3x3_wrw_w4, chunked by
+        # whole images.  ADAPTDL_WRW_W4=1/0 forces it on/off.  Default
+        # on: 103/105 us vs MIOpen's 168/171 us at N1024 C=K=512, and
+        # 41.3 vs 41.9 ms/step in context (profiles/wrw_w4_time.json).
+        if h == 4 and w == 4 and \
+                os.getenv("ADAPTDL_WRW_W4", _WRW_W4_DEFAULT) != "1":
+            return False
         return bool(ext.conv_wrw_ok(n, h, w, c, self.out_channels))
 
     def _s2_ok(self, x):

@@ -6,7 +6,11 @@ dev = torch.device("cuda")
 shapes = [(1024, 64, 32, 32, 64), (1024, 128, 16, 16, 128), (1024, 256, 8, 8, 256),
           # ImageNet-resolution (ResNet-50 at 224) padded-width shapes
           (256, 64, 56, 56, 64), (256, 128, 28, 28, 128),
-          (256, 256, 14, 14, 256), (256, 512, 7, 7, 512)]
+          (256, 256, 14, 14, 256), (256, 512, 7, 7, 512),
+          # CIFAR layer4 (ResNet-18/34): k_conv3x3_wrw_w4
+          (1024, 512, 4, 4, 512), (1024, 256, 4, 4, 256)]
+if len(sys.argv) > 1:           # wrw_time.py W [W ...]: only these widths
+    shapes = [s for s in shapes if str(s[3]) in sys.argv[1:]]
 for n, c, h, w, k in shapes:
     x = torch.randn(n, c, h, w, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
     dy = torch.randn(n, k, h, w, device=dev).to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
