@@ -75,7 +75,7 @@ class CifarResNet(nn.Module):
     def __init__(self, block, num_blocks, num_classes=10):
         super().__init__()
         self.in_planes = 64
-        self.conv1 = nn.Conv2d(3, 64, 3, stride=1, padding=1, bias=False)
+        self.conv1 = FusedConv2d(3, 64, 3, stride=1, padding=1, bias=False)
         self.bn1 = _bn(64, relu=True)
         self.layer1 = self._make_layer(block, 64, num_blocks[0], 1)
         self.layer2 = self._make_layer(block, 128, num_blocks[1], 2)
@@ -104,7 +104,7 @@ class ImageNetResNet(nn.Module):
     def __init__(self, block, num_blocks, num_classes=1000):
         super().__init__()
         self.in_planes = 64
-        self.conv1 = nn.Conv2d(3, 64, 7, stride=2, padding=3, bias=False)
+        self.conv1 = FusedConv2d(3, 64, 7, stride=2, padding=3, bias=False)
         self.bn1 = _bn(64, relu=True)
         self.maxpool = nn.MaxPool2d(3, stride=2, padding=1)
         self.layer1 = self._make_layer(block, 64, num_blocks[0], 1)

@@ -220,6 +220,19 @@ void fused_adamw_mw(torch::Tensor p, torch::Tensor g, torch::Tensor w,
                           bias1, bias2, (int)adam_mode, stream());
 }
 
+// dst += src.float(): dst an fp32 gradient-bucket segment, src the dense
+// bf16/fp16 gradient a library call produced (same element order).
+void accum_cast(torch::Tensor dst, torch::Tensor src) {
+    check_f32(dst, "dst");
+    const StatDtype dtype = check_stat_in(src, "src");
+    TORCH_CHECK(dtype != STAT_F32, "src must be bfloat16 or float16");
+    TORCH_CHECK(dst.numel() == src.numel(), "dst/src size mismatch");
+    long n = dst.numel();
+    if (n == 0) return;
+    launch_accum_cast(dtype, dst.data_ptr<float>(), src.data_ptr(), n,
+                      stream());
+}
+
 // ---- fused NHWC BatchNorm(+ReLU) -------------------------------------
 
 void check_bn_x(const torch::Tensor& t, const char* name) {
@@ -317,13 +330,14 @@ void bn_fwd(torch::Tensor x, torch::Tensor z, torch::Tensor y,
 
 // z: the forward's residual, or empty when `mask` (the forward's saved
 // ReLU bitmask) stands in for it; dz non-empty = also write dL/dz.
+// accum: dgamma/dbeta (gradient-bucket segments) += instead of =.
 void bn_bwd(torch::Tensor x, torch::Tensor z, torch::Tensor dy,
             torch::Tensor dx, torch::Tensor dz,
             torch::Tensor gamma, torch::Tensor save_mean,
             torch::Tensor save_rstd, torch::Tensor scale,
             torch::Tensor shift, bool train, bool relu, torch::Tensor ws,
             torch::Tensor dgamma, torch::Tensor dbeta,
-            torch::Tensor pqr, torch::Tensor mask) {
+            torch::Tensor pqr, torch::Tensor mask, bool accum) {
     check_bn_x(x, "x"); check_bn_x(dy, "dy"); check_bn_x(dx, "dx");
     TORCH_CHECK(dy.sizes() == x.sizes() && dx.sizes() == x.sizes(),
                 "gradient shape mismatch");
@@ -362,7 +376,7 @@ void bn_bwd(torch::Tensor x, torch::Tensor z, torch::Tensor dy,
                   shift.data_ptr<float>(), (int)train, (int)relu,
                   ws.data_ptr<float>(),
                   dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
-                  pqr.data_ptr<float>(), mp, stream());
+                  pqr.data_ptr<float>(), mp, (int)accum, stream());
 }
 
 // ---- custom MFMA conv 3x3 wrw ---------------------------------------
@@ -377,24 +391,31 @@ long conv_wrw_nsplit(long N, long H, long W, long C, long K) {
 
 // dw = wrw(x, dy): x (N,C,H,W) channels_last bf16, dy (N,K,H,W)
 // channels_last bf16, dw (K,C,3,3) channels_last fp32, ws workspace.
+// accum: dw += instead; dw is then the weight's gradient-bucket segment,
+// K*9*C contiguous floats in the same (K,3,3,C) storage order.
 void conv_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor ws,
-              torch::Tensor dw) {
+              torch::Tensor dw, bool accum) {
     check_bn_x(x, "x"); check_bn_x(dy, "dy");
     const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
     const long K = dy.size(1);
     TORCH_CHECK(dy.size(0) == N && dy.size(2) == H && dy.size(3) == W,
                 "dy shape mismatch");
     TORCH_CHECK(conv_wrw_ok(N, H, W, C, K), "unsupported wrw shape");
-    TORCH_CHECK(dw.is_cuda() && dw.scalar_type() == torch::kFloat32 &&
-                dw.is_contiguous(at::MemoryFormat::ChannelsLast) &&
-                dw.size(0) == K && dw.size(1) == C && dw.size(2) == 3 &&
-                dw.size(3) == 3, "dw must be (K,C,3,3) channels_last f32");
+    if (accum)
+        check_vecf(dw, K * 9 * C, "dw segment");
+    else
+        TORCH_CHECK(dw.is_cuda() && dw.scalar_type() == torch::kFloat32 &&
+                    dw.is_contiguous(at::MemoryFormat::ChannelsLast) &&
+                    dw.size(0) == K && dw.size(1) == C &&
+                    dw.size(2) == 3 && dw.size(3) == 3,
+                    "dw must be (K,C,3,3) channels_last f32");
     const long nsplit = conv_wrw_nsplit(N, H, W, C, K);
     check_vecf(ws, nsplit * K * 9 * C, "ws");
     launch_conv3x3_wrw((const unsigned short*)x.data_ptr(),
                        (const unsigned short*)dy.data_ptr(),
                        ws.data_ptr<float>(), dw.data_ptr<float>(),
-                       (int)N, (int)H, (int)W, (int)C, (int)K, stream());
+                       (int)N, (int)H, (int)W, (int)C, (int)K, (int)accum,
+                       stream());
 }
 
 bool conv_mm_ok(long N, long H, long W, long C, long K) {
@@ -565,12 +586,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("fused_adamw_mw", &fused_adamw_mw,
             "fused Adam(W) step, bf16/fp16 bucket with fp32 master weights");
     mod.def("bn_fwd", &bn_fwd, "fused NHWC bf16 BatchNorm(+ReLU) forward");
-    mod.def("bn_bwd", &bn_bwd, "fused NHWC bf16 BatchNorm(+ReLU) backward");
+    mod.def("bn_bwd", &bn_bwd, "fused NHWC bf16 BatchNorm(+ReLU) backward",
+            py::arg("x"), py::arg("z"), py::arg("dy"), py::arg("dx"),
+            py::arg("dz"), py::arg("gamma"), py::arg("save_mean"),
+            py::arg("save_rstd"), py::arg("scale"), py::arg("shift"),
+            py::arg("train"), py::arg("relu"), py::arg("ws"),
+            py::arg("dgamma"), py::arg("dbeta"), py::arg("pqr"),
+            py::arg("mask"), py::arg("accum") = false);
+    mod.def("accum_cast", &accum_cast,
+            "dst_f32 += float(src16), bucket-segment gradient sink");
     mod.def("bn_num_rblocks", &bn_ws_rows,
             "rows of the BN stage-1 partials workspace for (M, C)");
     mod.def("conv_wrw_ok", &conv_wrw_ok, "3x3 wrw fast-path predicate");
     mod.def("conv_wrw_nsplit", &conv_wrw_nsplit, "wrw workspace splits");
-    mod.def("conv_wrw", &conv_wrw, "MFMA 3x3 s1 NHWC weight gradient");
+    mod.def("conv_wrw", &conv_wrw, "MFMA 3x3 s1 NHWC weight gradient",
+            py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("dw"),
+            py::arg("accum") = false);
     mod.def("conv_mm_ok", &conv_mm_ok, "3x3 fwd/bwd-data predicate");
     mod.def("conv_mm", &conv_mm, "MFMA 3x3 s1 NHWC conv (fwd/bwd-data)");
     mod.def("conv_s2_fwd_ok", &conv_s2_fwd_ok,

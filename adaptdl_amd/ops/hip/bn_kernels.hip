@@ -381,7 +381,7 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_bwd_tail(
         const float* __restrict__ gamma, const float* __restrict__ mean,
         const float* __restrict__ rstd, int train,
         float* __restrict__ dgamma, float* __restrict__ dbeta,
-        float* __restrict__ pqr) {
+        float* __restrict__ pqr, int accum) {
     __shared__ float lds[2 * BLOCK / WAVE];
     const int i = blockIdx.x;
     const float g = gamma[i], rs = rstd[i], mn = mean[i];
@@ -390,8 +390,10 @@ extern "C" __global__ __launch_bounds__(BLOCK) void k_bn_bwd_tail(
     // as in the forward tail: every product below rounds on its own
     if (threadIdx.x == 0) {
         #pragma clang fp contract(off)
-        dbeta[i] = sum_g;
-        dgamma[i] = sum_gx;
+        // accum: dgamma/dbeta are a gradient bucket's segments; one
+        // fp32 add each, as the separate accumulation kernel rounded.
+        dbeta[i] = accum ? dbeta[i] + sum_g : sum_g;
+        dgamma[i] = accum ? dgamma[i] + sum_gx : sum_gx;
         float p = g * rs;
         float q = 0.f, r = 0.f;
         if (train) {
@@ -526,7 +528,7 @@ extern "C" void launch_bn_bwd(
         const float* gamma, const float* save_mean, const float* save_rstd,
         const float* scale, const float* shift, int train, int relu,
         float* ws, float* dgamma, float* dbeta, float* pqr,
-        const unsigned char* mask, hipStream_t s) {
+        const unsigned char* mask, int accum, hipStream_t s) {
     const int rpb = bn_rows_per_block(c);
     const unsigned nb = (unsigned)bn_num_rblocks(m, c);
     if (!relu) mask = nullptr;
@@ -535,7 +537,7 @@ extern "C" void launch_bn_bwd(
                        scale, shift, relu, mask, ws);
     hipLaunchKernelGGL(k_bn_bwd_tail, dim3(c), dim3(BLOCK), 0, s,
                        ws, (int)nb, m, c, gamma, save_mean, save_rstd,
-                       train, dgamma, dbeta, pqr);
+                       train, dgamma, dbeta, pqr, accum);
     hipLaunchKernelGGL(k_bn_bwd_apply, dim3(bn_grid(m, rpb, MAX_BLOCKS)),
                        dim3(BLOCK), 0, s, x, z, dy, dx, dz, m, c, scale,
                        shift, pqr, relu, mask);

@@ -652,10 +652,16 @@ extern "C" __global__ __launch_bounds__(512, 2) void k_conv3x3_wrw_w4(
 // dW[i] = sum_s ws[s * n + i].  Hierarchical: each block sums a
 // <=64-split group over a 1024-float i-chunk (f32x4 per thread), then
 // atomically adds into dw (zeroed by the launcher when several groups).
+// accum: dw is a gradient bucket segment and receives dw + sum; several
+// groups then add straight into it, with no zeroing.  A segment may be
+// only 4-byte aligned: the f32x4 access to dw needs 16 bytes, else the
+// launch reads and writes dw by element (decided from the argument, so
+// uniform over the grid).  ws is always read by vector.
 extern "C" __global__ __launch_bounds__(256) void k_wrw_reduce(
         const float* __restrict__ ws, float* __restrict__ dw, long n,
-        int nsplit, int ngroups, long nchunks) {
+        int nsplit, int ngroups, long nchunks, int accum) {
     const long work = nchunks * ngroups;
+    const bool dw_vec = ((size_t)dw & 15) == 0;
     for (long b = blockIdx.x; b < work; b += gridDim.x) {
         const long ic = b % nchunks;
         const int sg = (int)(b / nchunks);
@@ -675,10 +681,17 @@ extern "C" __global__ __launch_bounds__(256) void k_wrw_reduce(
             }
         }
         if (ngroups == 1) {
-            if (!tail) {
-                *reinterpret_cast<f32x4*>(dw + i0) = acc;
+            if (!tail && dw_vec) {
+                f32x4* d = reinterpret_cast<f32x4*>(dw + i0);
+                if (accum) {
+                    const f32x4 o = *d;
+                    acc[0] = o[0] + acc[0]; acc[1] = o[1] + acc[1];
+                    acc[2] = o[2] + acc[2]; acc[3] = o[3] + acc[3];
+                }
+                *d = acc;
             } else {
-                for (long j = 0; i0 + j < n; ++j) dw[i0 + j] = acc[j];
+                for (long j = 0; j < 4 && i0 + j < n; ++j)
+                    dw[i0 + j] = accum ? dw[i0 + j] + acc[j] : acc[j];
             }
         } else {
             for (long j = 0; j < 4 && i0 + j < n; ++j)
@@ -740,7 +753,7 @@ extern "C" int conv3x3_wrw_nsplit(int N, int H, int W, int C, int K) {
 
 extern "C" void launch_conv3x3_wrw(
         const ushort_t* x, const ushort_t* dy, float* ws, float* dw,
-        int N, int H, int W, int C, int K, hipStream_t s) {
+        int N, int H, int W, int C, int K, int accum, hipStream_t s) {
     int P = 8, Wp = 8;
     conv3x3_wrw_params(H, W, &P, &Wp);
     const int nsplit = conv3x3_wrw_nsplit(N, H, W, C, K);
@@ -756,12 +769,12 @@ extern "C" void launch_conv3x3_wrw(
     // version ran 144 blocks on layer1 and measured 5x off bandwidth).
     const int ngroups = (nsplit + 15) / 16;
     const long nchunks = (n + 1023) / 1024;
-    if (ngroups > 1)
+    if (ngroups > 1 && !accum)
         hipMemsetAsync(dw, 0, n * sizeof(float), s);
     long blocks = nchunks * ngroups;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_wrw_reduce, dim3((unsigned)blocks), dim3(256), 0,
-                       s, ws, dw, n, nsplit, ngroups, nchunks);
+                       s, ws, dw, n, nsplit, ngroups, nchunks, accum);
 }
 
 // =====================================================================
@@ -2349,7 +2362,7 @@ extern "C" void launch_conv3x3_s2_wrw(
     long blocks = nchunks * ngroups;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_wrw_reduce, dim3((unsigned)blocks), dim3(256), 0,
-                       s, ws, dw, n, nsplit, ngroups, nchunks);
+                       s, ws, dw, n, nsplit, ngroups, nchunks, 0);
 }
 
 // =====================================================================

@@ -619,6 +619,59 @@ UPDATE_KERNEL k_fused_adamw_mw_fp16(
                                     lr / bias1, rsqrtf(bias2), adam_mode});
 }
 
+// ---- gradient sink: dst (fp32 bucket segment) += float(src) ----------
+// A library weight gradient arrives in bf16/fp16; this folds it into the
+// fp32 bucket in one pass: the conversion is exact and each element takes
+// one fp32 add, so the result equals src.float() added by a separate
+// kernel.  Traversal of update_pass_mw: scalar head until src is 16-byte
+// aligned, then 8 elements per lane if dst is aligned there too (else
+// the whole launch is scalar — grid-uniform), scalar tail.
+template <class T>
+__device__ __forceinline__ void accum_cast(
+        float* __restrict__ dst, const typename T::elem* __restrict__ src,
+        long n) {
+    typedef typename T::elem E;
+    typedef typename T::vec V;
+    typedef F32::vec V4;
+    constexpr int W = T::W;
+    const long i = (long)blockIdx.x * BLOCK + threadIdx.x;
+    const long stride = (long)gridDim.x * BLOCK;
+
+    long head = (16 - ((size_t)src & 15)) / sizeof(E) & (W - 1);
+    if (((size_t)(dst + head) & 15) != 0) head = n;
+    if (head > n) head = n;
+    for (long j = i; j < head; j += stride) dst[j] = dst[j] + T::to_f(src[j]);
+
+    const long nv = (n - head) / W;
+    for (long j = i; j < nv; j += stride) {
+        const V vs = ((const V*)(src + head))[j];
+        #pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            V4 vd = ((const V4*)(dst + head))[2 * j + h];
+            #pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                E e = vs[4 * h + k];
+                vd[k] = vd[k] + T::to_f(e);
+            }
+            ((V4*)(dst + head))[2 * j + h] = vd;
+        }
+    }
+
+    for (long j = head + nv * W + i; j < n; j += stride)
+        dst[j] = dst[j] + T::to_f(src[j]);
+}
+
+UPDATE_KERNEL k_accum_cast_bf16(float* __restrict__ dst,
+                                const unsigned short* __restrict__ src,
+                                long n) {
+    accum_cast<BF16>(dst, src, n);
+}
+UPDATE_KERNEL k_accum_cast_fp16(float* __restrict__ dst,
+                                const unsigned short* __restrict__ src,
+                                long n) {
+    accum_cast<FP16>(dst, src, n);
+}
+
 // ---- host-side launchers (called from bindings.cpp, which is compiled
 // by the host compiler and cannot launch kernels itself) ---------------
 
@@ -643,6 +696,17 @@ extern "C" void launch_sqsum(StatDtype dtype, const void* x, long n, double* out
     case STAT_F32: launch(k_sqsum, n, s, (const float*)x, n, out); break;
     case STAT_BF16: launch(k_sqsum_bf16, n, s, (const u16*)x, n, out); break;
     case STAT_FP16: launch(k_sqsum_fp16, n, s, (const u16*)x, n, out); break;
+    }
+}
+
+extern "C" void launch_accum_cast(StatDtype dtype, float* dst,
+                                  const void* src, long n, hipStream_t s) {
+    switch (dtype) {
+    case STAT_BF16:
+        launch(k_accum_cast_bf16, n, s, dst, (const u16*)src, n); break;
+    case STAT_FP16:
+        launch(k_accum_cast_fp16, n, s, dst, (const u16*)src, n); break;
+    case STAT_F32: break;
     }
 }
 

@@ -59,6 +59,10 @@ void launch_fused_adamw_mw(StatDtype dtype, void* p, const void* g,
                            float weight_decay, float bias1, float bias2,
                            int adam_mode, hipStream_t s);
 
+// dst[i] += float(src[i]); src is STAT_BF16 / STAT_FP16 raw storage.
+void launch_accum_cast(StatDtype dtype, float* dst, const void* src, long n,
+                       hipStream_t s);
+
 // ---- bn_kernels.hip (bf16 NHWC as raw unsigned short) ----------------
 
 // Rows of the stage-1 partials workspace (= stage-1 grid size) for M rows
@@ -68,6 +72,8 @@ long bn_num_rblocks(long m, int c);
 // [row * (C/8) + slot], bit k = channel slot*8+k kept.  The forward writes
 // it; the backward, given one, reads it instead of z (z may then be null).
 // num_batches_tracked: nullable int64 scalar the training forward bumps.
+// accum (backward): dgamma/dbeta += the sums instead of = (gradient sink;
+// the two may then be any 4-byte-aligned fp32 addresses).
 void launch_bn_fwd(const unsigned short* x, const unsigned short* z,
                    unsigned short* y, long m, int c, const float* gamma,
                    const float* beta, float* running_mean,
@@ -82,16 +88,19 @@ void launch_bn_bwd(const unsigned short* x, const unsigned short* z,
                    const float* save_mean, const float* save_rstd,
                    const float* scale, const float* shift, int train,
                    int relu, float* ws, float* dgamma, float* dbeta,
-                   float* pqr, const unsigned char* mask, hipStream_t s);
+                   float* pqr, const unsigned char* mask, int accum,
+                   hipStream_t s);
 
 // ---- conv_kernels.hip ------------------------------------------------
 
 int conv3x3_wrw_params(int H, int W, int* P, int* Wp);
 int conv3x3_wrw_supported(int H, int W, int C, int K);
 int conv3x3_wrw_nsplit(int N, int H, int W, int C, int K);
+// accum: dw += wrw(x, dy) instead of dw = (gradient sink; dw may then be
+// only 4-byte aligned).
 void launch_conv3x3_wrw(const unsigned short* x, const unsigned short* dy,
                         float* ws, float* dw, int N, int H, int W, int C,
-                        int K, hipStream_t s);
+                        int K, int accum, hipStream_t s);
 int conv3x3_mm_supported(int H, int W, int C, int K);
 void launch_conv3x3_mm(const unsigned short* x, const unsigned short* w,
                        unsigned short* y, int N, int H, int W, int C,

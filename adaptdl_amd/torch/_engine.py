@@ -29,7 +29,9 @@ produced no gradient in the current cycle.
 """
 
 import logging
+import os
 import time
+import weakref
 
 import torch
 import torch.distributed
@@ -48,6 +50,82 @@ _cycle_serial = 0
 
 def cycle_serial():
     return _cycle_serial
+
+
+# Gradient sinks: kernels that produce a parameter gradient add it to the
+# parameter's bucket segment themselves instead of handing a fresh tensor
+# to autograd, whose AccumulateGrad then launches one add per parameter
+# per microbatch (the .grad views are never None, so it never steals).
+# ADAPTDL_GRAD_SINK=0/1 forces it off/on.
+_GRAD_SINK_DEFAULT = "1"   # set by measurement, profiles/grad_sink_ab.json
+
+# The engine whose sinks are handed out: set by AdaptiveDataParallel for
+# the duration of one training-mode forward.
+_armed = None
+_engines = weakref.WeakSet()   # engines whose buckets are live
+
+
+class armed(object):
+    """Context manager arming ``engine``'s sinks (None: disarm)."""
+
+    def __init__(self, engine):
+        self._engine = engine
+
+    def __enter__(self):
+        global _armed
+        self._outer, _armed = _armed, self._engine
+
+    def __exit__(self, *exc):
+        global _armed
+        _armed = self._outer
+
+
+def grad_sink(param):
+    """The fp32 bucket segment a backward kernel may add ``param``'s
+    gradient into (1-D, contiguous, in the parameter's storage order -
+    see :func:`_segment_view`), or None when the gradient must go through
+    autograd: outside an AdaptiveDataParallel training forward, non-fp32
+    bucket, tensor hooks on the parameter, or ADAPTDL_GRAD_SINK=0.
+
+    A caller that gets a segment adds the gradient into it in backward,
+    returns None to autograd for that parameter, and then calls
+    :func:`grad_written` once per segment it asked for.
+    """
+    sinks = grad_sinks((param,))
+    return sinks[0] if sinks is not None else None
+
+
+def grad_sinks(params):
+    """:func:`grad_sink` for several parameters that one kernel writes
+    together: all of their segments, or None if any has none."""
+    engine = _armed
+    if engine is None:
+        return None
+    if os.getenv("ADAPTDL_GRAD_SINK", _GRAD_SINK_DEFAULT) != "1":
+        return None
+    out = []
+    for param in params:
+        seg = engine._param_to_segment.get(param)
+        if seg is None or seg[0].flat.dtype != torch.float32 or \
+                param._backward_hooks:
+            return None
+        bucket, off, n = seg
+        out.append(bucket.flat[off:off + n])
+    for param in params:
+        engine._sink_pending[param] = \
+            engine._sink_pending.get(param, 0) + 1
+    return out
+
+
+def grad_written(param):
+    """Tell ``param``'s engine that the kernel adding into its sink is
+    enqueued; does what the post-accumulate hook does for other
+    parameters, once per backward pass."""
+    for engine in _engines:
+        if param in engine._param_to_segment:
+            engine._grad_written(param)
+            return
+    raise RuntimeError("grad_written: parameter has no live engine")
 
 
 def _segment_view(seg, p):
@@ -149,6 +227,11 @@ class GradSyncEngine(object):
         self._hooks = []
         self.buckets = []
         self._param_to_bucket = {}
+        self._param_to_segment = {}   # param -> (bucket, offset, numel)
+        # Sinks handed out this forward and not yet written, per param: a
+        # module applied twice writes twice and is ready after the second.
+        self._sink_pending = {}
+        _engines.add(self)
 
         n_groups = len(param_groups)
         device = None
@@ -203,21 +286,43 @@ class GradSyncEngine(object):
             offset += n
         bucket = Bucket(gidx, flat, segments)
         self.buckets.append(bucket)
-        for p in params:
+        for p, off, n in segments:
             self._param_to_bucket[p] = bucket
+            self._param_to_segment[p] = (bucket, off, n)
 
     # ---- backward-time flow ---------------------------------------------
 
     def _grad_ready_hook(self, param):
+        """Post-accumulate hook: autograd added ``param``'s gradient."""
+        if param in self._sink_pending:
+            # Sunk in this pass: autograd runs the accumulation node,
+            # and this hook, for the None it was given too, and
+            # _grad_written is what counts the parameter.
+            return
+        self._queue_end_of_backward()
+        self._param_ready(param)
+
+    def _queue_end_of_backward(self):
         if not self._callback_queued:
             torch.autograd.Variable._execution_engine.queue_callback(
                 self._end_of_backward)
             self._callback_queued = True
+
+    def _param_ready(self, param):
         bucket = self._param_to_bucket[param]
         bucket.ready += 1
         bucket.used = True
         if bucket.ready == len(bucket.segments):
             self._flush_bucket(bucket)
+
+    def _grad_written(self, param):
+        """A sink's counterpart of the post-accumulate hook: the parameter
+        counts as ready once, after the last of its sinks is written."""
+        self._queue_end_of_backward()
+        left = self._sink_pending.get(param, 1) - 1
+        self._sink_pending[param] = left
+        if left == 0:
+            self._param_ready(param)
 
     def _flush_bucket(self, bucket):
         if not self.require_sync or bucket.work is not None:
@@ -233,6 +338,7 @@ class GradSyncEngine(object):
 
     def _end_of_backward(self):
         self._callback_queued = False
+        self._sink_pending.clear()
         if not self.require_sync:
             # Accumulation-only microbatch: record its statistics and keep
             # accumulating gradients in the buckets.
@@ -349,6 +455,8 @@ class GradSyncEngine(object):
         for h in self._hooks:
             h.remove()
         self._hooks.clear()
+        self._param_to_segment.clear()   # no sinks from a detached engine
+        _engines.discard(self)
         for bucket in self.buckets:
             for p, _, _ in bucket.segments:
                 p.grad = None

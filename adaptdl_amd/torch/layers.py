@@ -24,6 +24,63 @@ import torch.nn.functional as F
 from adaptdl_amd import ops
 
 
+def _same_order(g, p):
+    """g is dense and stores its elements in p's memory order."""
+    if g.shape != p.shape:
+        return False
+    if any(sg != sp for n, sg, sp in zip(g.shape, g.stride(), p.stride())
+           if n > 1):
+        return False
+    return p.is_contiguous() or p.dim() in (4, 5) and (
+        p.is_contiguous(memory_format=torch.channels_last)
+        if p.dim() == 4 else
+        p.is_contiguous(memory_format=torch.channels_last_3d))
+
+
+class _ParamSinkFunction(torch.autograd.Function):
+    """Hands ``value`` (the parameter, or a cast of it) to the ops that
+    follow, and adds the gradient they return for it into ``sink``, the
+    parameter's gradient-bucket segment (see _engine.grad_sink), instead
+    of passing it on to autograd's per-parameter accumulation.
+
+    A dense 16-bit gradient in the parameter's memory order (the bf16
+    dW of a library conv under autocast) takes one k_accum_cast pass;
+    any other is added as autograd would have added it to ``.grad``.
+    """
+
+    @staticmethod
+    def forward(ctx, param, value, sink):
+        ctx.param = param
+        ctx.sink = sink
+        return value.detach()
+
+    @staticmethod
+    def backward(ctx, g):
+        from adaptdl_amd.torch import _engine
+        param, sink = ctx.param, ctx.sink
+        if g.is_cuda and g.dtype in (torch.bfloat16, torch.float16) \
+                and _same_order(g, param):
+            flat = g.as_strided((g.numel(),), (1,), g.storage_offset())
+            ops._require_ext(flat).accum_cast(sink, flat)
+        else:
+            _engine._segment_view(sink, param).add_(g)
+        _engine.grad_written(param)
+        return None, None, None
+
+
+def _sunk(param, cast=None):
+    """``param`` routed through its gradient sink when it has one (as
+    ``cast()``, a detached low-precision copy, if given), else ``param``
+    itself."""
+    from adaptdl_amd.torch import _engine
+    sink = _engine.grad_sink(param) \
+        if param.requires_grad and torch.is_grad_enabled() else None
+    if sink is None:
+        return param
+    return _ParamSinkFunction.apply(
+        param, param if cast is None else cast(), sink)
+
+
 def _hip_bn_ok(x):
     c = x.shape[1] if x.dim() == 4 else 0
     return (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4 and
@@ -36,7 +93,7 @@ class _FusedBNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, z, weight, bias, running_mean, running_var,
                 training, momentum, eps, relu, num_batches_tracked=None,
-                save_mask=False):
+                save_mask=False, sinks=None):
         ext = ops._load_extension()
         y = torch.empty_like(x)
         c = x.shape[1]
@@ -70,6 +127,10 @@ class _FusedBNFunction(torch.autograd.Function):
         ctx.bn_train = bool(training)
         ctx.bn_relu = bool(relu)
         ctx.bn_has_z = z is not None
+        # gradient-bucket segments of (weight, bias): the backward tail
+        # adds dgamma/dbeta into them
+        ctx.bn_sinks = sinks
+        ctx.bn_params = (weight, bias) if sinks is not None else None
         return y
 
     @staticmethod
@@ -85,14 +146,22 @@ class _FusedBNFunction(torch.autograd.Function):
         m = x.numel() // c
         opt = dict(dtype=torch.float32, device=x.device)
         ws = torch.empty(2 * c * ext.bn_num_rblocks(m, c), **opt)
-        dgamma = torch.empty(c, **opt)
-        dbeta = torch.empty(c, **opt)
+        sunk = ctx.bn_sinks is not None
+        dgamma, dbeta = ctx.bn_sinks if sunk else \
+            (torch.empty(c, **opt), torch.empty(c, **opt))
         pqr = torch.empty(3 * c, **opt)
         ext.bn_bwd(x, z, dy, dx, dz, weight, save_mean, save_rstd, scale,
                    shift, ctx.bn_train, ctx.bn_relu, ws, dgamma, dbeta,
-                   pqr, mask)
+                   pqr, mask, sunk)
+        if sunk:
+            # after the launch: the bucket's statistics pass is ordered
+            # behind it on the stream
+            from adaptdl_amd.torch import _engine
+            for p in ctx.bn_params:
+                _engine.grad_written(p)
+            dgamma = dbeta = None
         return (dx, dz if ctx.bn_has_z else None, dgamma, dbeta) + \
-            (None,) * 8
+            (None,) * 9
 
 
 class FusedBatchNormAct2d(nn.BatchNorm2d):
@@ -122,11 +191,25 @@ class FusedBatchNormAct2d(nn.BatchNorm2d):
             needs_bwd = torch.is_grad_enabled() and any(
                 t is not None and t.requires_grad
                 for t in (x, residual, self.weight, self.bias))
+            sinks = None
+            if needs_bwd and self.weight.requires_grad and \
+                    self.bias.requires_grad:
+                from adaptdl_amd.torch import _engine
+                sinks = _engine.grad_sinks((self.weight, self.bias))
             return _FusedBNFunction.apply(
                 x, residual, self.weight, self.bias, self.running_mean,
                 self.running_var, use_batch_stats, momentum, self.eps,
-                self.relu, nbt, needs_bwd)
-        y = super().forward(x)
+                self.relu, nbt, needs_bwd, sinks)
+        if self.affine and self.training and self.track_running_stats \
+                and self.momentum is not None:
+            # nn.BatchNorm2d.forward with the affine parameters routed
+            # through their gradient sinks
+            self.num_batches_tracked.add_(1)
+            y = F.batch_norm(x, self.running_mean, self.running_var,
+                             _sunk(self.weight), _sunk(self.bias), True,
+                             self.momentum, self.eps)
+        else:
+            y = super().forward(x)
         if residual is not None:
             y = y + residual
         return F.relu(y) if self.relu else y
@@ -141,10 +224,14 @@ class _FusedConvFunction(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x, weight, wb, stride, padding, dilation, groups):
+    def forward(ctx, x, weight, wb, stride, padding, dilation, groups,
+                sink=None):
         ext = ops._load_extension()
         n, c, h, w = x.shape
         k = wb.shape[0]
+        # weight's gradient-bucket segment: the wrw reduce adds into it
+        ctx.conv_sink = sink
+        ctx.conv_param = weight if sink is not None else None
         # The custom fwd/bwd-data kernel is numerics-verified and beats
         # MIOpen's UNTUNED find choice on C=64 (213 vs 229 us), but
         # loses to its tuned in-context pick (154 us) -- end-to-end it
@@ -189,11 +276,16 @@ class _FusedConvFunction(torch.autograd.Function):
         nsplit = ext.conv_wrw_nsplit(n, h, w, c, k)
         ws = torch.empty(nsplit * k * 9 * c, dtype=torch.float32,
                          device=x.device)
+        if ctx.conv_sink is not None:
+            from adaptdl_amd.torch import _engine
+            ext.conv_wrw(x, dy, ws, ctx.conv_sink, True)
+            _engine.grad_written(ctx.conv_param)
+            return dx, None, None, None, None, None, None, None
         dw = torch.empty(k, c, 3, 3, dtype=torch.float32,
                          device=x.device) \
             .contiguous(memory_format=torch.channels_last)
         ext.conv_wrw(x, dy, ws, dw)
-        return dx, dw, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None
 
 
 class _S2ConvFunction(torch.autograd.Function):
@@ -390,16 +482,31 @@ class FusedConv2d(nn.Conv2d):
                 x.dtype != torch.bfloat16 and \
                 torch.get_autocast_dtype("cuda") == torch.bfloat16:
             x = x.to(torch.bfloat16)
+        from adaptdl_amd.torch import _engine
         if self._wrw_ok(x) and (self.weight.requires_grad or
                                 x.requires_grad):
+            sink = None
+            if self.weight.requires_grad and torch.is_grad_enabled() \
+                    and self.weight.is_contiguous(
+                        memory_format=torch.channels_last):
+                sink = _engine.grad_sink(self.weight)
             return _FusedConvFunction.apply(x, self.weight,
                                             self._cast_weight(),
                                             self.stride, self.padding,
-                                            self.dilation, self.groups)
+                                            self.dilation, self.groups,
+                                            sink)
+        # The remaining convs take the library's weight gradient (bf16
+        # under autocast).  With a gradient sink they get the cached
+        # bf16 weight, which autocast would otherwise re-cast on every
+        # microbatch, and their dW is cast-accumulated into the bucket.
+        lp = x.is_cuda and x.dtype == torch.bfloat16 and \
+            torch.is_autocast_enabled() and \
+            torch.get_autocast_dtype("cuda") == torch.bfloat16
+        weight = _sunk(self.weight, self._cast_weight if lp else None)
         if x.requires_grad and self._s2_ok(x):
-            return _S2ConvFunction.apply(x, self.weight, self.stride,
+            return _S2ConvFunction.apply(x, weight, self.stride,
                                          self.padding, self.dilation,
                                          self.groups)
         if self._s2_1x1_ok(x):
-            return _S2Conv1x1Function.apply(x, self.weight)
-        return super().forward(x)
+            return _S2Conv1x1Function.apply(x, weight)
+        return self._conv_forward(x, weight, self.bias)

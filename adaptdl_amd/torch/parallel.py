@@ -27,6 +27,7 @@ import torch.distributed
 
 import adaptdl_amd.checkpoint
 import adaptdl_amd.env
+from adaptdl_amd.torch import _engine
 from adaptdl_amd.torch.data import current_dataloader
 from adaptdl_amd.torch.scaling_rules import (AdaScale, AdamScale,
                                              ScalingRuleBase)
@@ -108,7 +109,11 @@ class AdaptiveDataParallel(torch.nn.Module):
                            dataloader.batch_size)
             self.gns.set_accum_scale(accum_scale)
         self.gns.engine.require_sync = self.require_backward_grad_sync
-        return self.module(*args, **kwargs)
+        # Gradient sinks (layers add parameter gradients straight into
+        # the engine's buckets) are handed out for this forward only.
+        arm = self.training and torch.is_grad_enabled()
+        with _engine.armed(self.gns.engine if arm else None):
+            return self.module(*args, **kwargs)
 
     @print_exc
     def _after_sync(self):

@@ -23,11 +23,11 @@ int main() {
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     for (int i = 0; i < 3; ++i)
-        launch_conv3x3_wrw(x, dy, ws, dw, N, H, W, C, K, 0);
+        launch_conv3x3_wrw(x, dy, ws, dw, N, H, W, C, K, 0, 0);
     (void)hipDeviceSynchronize();
     (void)hipEventRecord(e0, 0);
     for (int i = 0; i < 20; ++i)
-        launch_conv3x3_wrw(x, dy, ws, dw, N, H, W, C, K, 0);
+        launch_conv3x3_wrw(x, dy, ws, dw, N, H, W, C, K, 0, 0);
     (void)hipEventRecord(e1, 0);
     (void)hipDeviceSynchronize();
     float ms = 0;
