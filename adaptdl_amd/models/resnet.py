@@ -47,13 +47,13 @@ class Bottleneck(nn.Module):
 
     def __init__(self, in_planes, planes, stride=1):
         super().__init__()
-        self.conv1 = nn.Conv2d(in_planes, planes, 1, bias=False)
+        self.conv1 = FusedConv2d(in_planes, planes, 1, bias=False)
         self.bn1 = _bn(planes, relu=True)
         self.conv2 = FusedConv2d(planes, planes, 3, stride=stride,
                                  padding=1, bias=False)
         self.bn2 = _bn(planes, relu=True)
-        self.conv3 = nn.Conv2d(planes, self.expansion * planes, 1,
-                               bias=False)
+        self.conv3 = FusedConv2d(planes, self.expansion * planes, 1,
+                                 bias=False)
         # bn3 fuses the residual add + final ReLU of the block.
         self.bn3 = _bn(self.expansion * planes, relu=True)
         self.shortcut = nn.Sequential()

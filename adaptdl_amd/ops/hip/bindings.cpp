@@ -418,6 +418,48 @@ void conv_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor ws,
                        stream());
 }
 
+// ---- custom MFMA conv 1x1 wrw (stride 1 and 2, pad 0) ----------------
+
+bool conv1x1_wrw_ok(long H, long W, long C, long K, long stride) {
+    return conv1x1_wrw_supported((int)H, (int)W, (int)C, (int)K,
+                                 (int)stride) != 0;
+}
+
+long conv1x1_wrw_nsplit_(long N, long Ho, long Wo, long C, long K) {
+    return conv1x1_wrw_nsplit((int)N, (int)Ho, (int)Wo, (int)C, (int)K);
+}
+
+// dw = wrw(x, dy): x (N,C,H,W) and dy (N,K,Ho,Wo) channels_last bf16 with
+// Ho = H / stride, dw (K,C,1,1) fp32, ws nsplit * K*C floats.  accum:
+// dw += instead; dw is then the weight's gradient-bucket segment, K*C
+// contiguous floats.
+void conv1x1_wrw(torch::Tensor x, torch::Tensor dy, torch::Tensor ws,
+                 torch::Tensor dw, long stride, bool accum) {
+    check_bn_x(x, "x"); check_bn_x(dy, "dy");
+    const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+    const long K = dy.size(1);
+    TORCH_CHECK(conv1x1_wrw_ok(H, W, C, K, stride),
+                "unsupported 1x1 wrw shape");
+    const long Ho = H / stride, Wo = W / stride;
+    TORCH_CHECK(dy.size(0) == N && dy.size(2) == Ho && dy.size(3) == Wo,
+                "dy shape mismatch");
+    if (accum)
+        check_vecf(dw, K * C, "dw segment");
+    else
+        TORCH_CHECK(dw.is_cuda() && dw.scalar_type() == torch::kFloat32 &&
+                    dw.is_contiguous() && dw.dim() == 4 &&
+                    dw.size(0) == K && dw.size(1) == C &&
+                    dw.size(2) == 1 && dw.size(3) == 1,
+                    "dw must be (K,C,1,1) contiguous f32");
+    const long nsplit = conv1x1_wrw_nsplit_(N, Ho, Wo, C, K);
+    check_vecf(ws, nsplit * K * C, "ws");
+    launch_conv1x1_wrw((const unsigned short*)x.data_ptr(),
+                       (const unsigned short*)dy.data_ptr(),
+                       ws.data_ptr<float>(), dw.data_ptr<float>(),
+                       (int)N, (int)H, (int)W, (int)C, (int)K, (int)stride,
+                       (int)accum, stream());
+}
+
 bool conv_mm_ok(long N, long H, long W, long C, long K) {
     return conv3x3_mm_supported((int)H, (int)W, (int)C, (int)K) != 0;
 }
@@ -602,6 +644,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
     mod.def("conv_wrw", &conv_wrw, "MFMA 3x3 s1 NHWC weight gradient",
             py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("dw"),
             py::arg("accum") = false);
+    mod.def("conv1x1_wrw_ok", &conv1x1_wrw_ok,
+            "1x1 wrw predicate (H, W, C, K, stride)");
+    mod.def("conv1x1_wrw_nsplit", &conv1x1_wrw_nsplit_,
+            "1x1 wrw workspace splits (N, Ho, Wo, C, K)");
+    mod.def("conv1x1_wrw", &conv1x1_wrw,
+            "MFMA 1x1 s1/s2 NHWC weight gradient",
+            py::arg("x"), py::arg("dy"), py::arg("ws"), py::arg("dw"),
+            py::arg("stride"), py::arg("accum") = false);
     mod.def("conv_mm_ok", &conv_mm_ok, "3x3 fwd/bwd-data predicate");
     mod.def("conv_mm", &conv_mm, "MFMA 3x3 s1 NHWC conv (fwd/bwd-data)");
     mod.def("conv_s2_fwd_ok", &conv_s2_fwd_ok,

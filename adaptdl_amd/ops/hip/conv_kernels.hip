@@ -702,6 +702,21 @@ extern "C" __global__ __launch_bounds__(256) void k_wrw_reduce(
 
 // ---- host-side launchers ---------------------------------------------
 
+// dw (+)= the sum of the nsplit slabs of n floats in ws.
+static void launch_wrw_reduce(const float* ws, float* dw, long n,
+                              int nsplit, int accum, hipStream_t s) {
+    // 16-slab groups: enough blocks to fill the chip (the 64-slab
+    // version ran 144 blocks on layer1 and measured 5x off bandwidth).
+    const int ngroups = (nsplit + 15) / 16;
+    const long nchunks = (n + 1023) / 1024;
+    if (ngroups > 1 && !accum)
+        hipMemsetAsync(dw, 0, n * sizeof(float), s);
+    long blocks = nchunks * ngroups;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_wrw_reduce, dim3((unsigned)blocks), dim3(256), 0,
+                       s, ws, dw, n, nsplit, ngroups, nchunks, accum);
+}
+
 // Per-shape chunking: Wp = padded line width (power of two >= W), P =
 // lines per chunk; CP = P * Wp <= 128 must be a multiple of 32.  The
 // CIFAR widths use full-width chunks (Wp == W); the ImageNet-resolution
@@ -764,17 +779,290 @@ extern "C" void launch_conv3x3_wrw(
     else
         hipLaunchKernelGGL(k_conv3x3_wrw, dim3(tiles * nsplit), dim3(512),
                            0, s, x, dy, ws, N, H, W, Wp, C, K, P, nsplit);
-    const long n = (long)K * 9 * C;
-    // 16-slab groups: enough blocks to fill the chip (the 64-slab
-    // version ran 144 blocks on layer1 and measured 5x off bandwidth).
-    const int ngroups = (nsplit + 15) / 16;
-    const long nchunks = (n + 1023) / 1024;
-    if (ngroups > 1 && !accum)
-        hipMemsetAsync(dw, 0, n * sizeof(float), s);
-    long blocks = nchunks * ngroups;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_wrw_reduce, dim3((unsigned)blocks), dim3(256), 0,
-                       s, ws, dw, n, nsplit, ngroups, nchunks, accum);
+    launch_wrw_reduce(ws, dw, (long)K * 9 * C, nsplit, accum, s);
+}
+
+// =====================================================================
+// 1x1 weight gradient, stride 1 and 2 (pad 0): k_conv1x1_wrw<TK, TC>.
+//
+//   dW[k][c] = sum_p dy[p][k] * x[q(p)][c],  p = (n*Ho + ho)*Wo + wo
+//
+// A pure GEMM reduced over the M = N*Ho*Wo flattened output pixels: no
+// taps, no halo, no line structure, hence any H and W.  Stride 1 has
+// q(p) = p; stride 2 reads x row (n, 2ho, 2wo), which changes only the
+// global address of a staged row (w1_xrow, two 32-bit divisions per
+// staged pixel, none per element).
+//
+//   - chunk = W1_CP = 128 consecutive flattened pixels (4 MFMA K steps);
+//     pixels >= M stage zero in both operands; block `split` of a tile
+//     takes chunks split, split + nsplit, ...
+//   - both operands stage transposed, dy_t[k][pixel] and x_t[c][pixel],
+//     in the dy_t layout of the 3x3 kernels (row stride DY_STRIDE, DSWZ,
+//     packed pixel-pair b32 writes by 8 pixel pairs x 8 channel groups
+//     per wave), so the A fragment (m = k) and the B fragment (n = c)
+//     are one aligned ds_read_b128 each.  Rows 64..127 of a 128-row tile
+//     fall on the banks and swizzle phases of rows 0..63 (64 * 80 dwords
+//     = 0 mod 64 banks, DSWZ has period 64 rows).
+//   - a wave owns 32k x 64c = 2 x 4 accumulator fragments: 6 b128 reads
+//     feed 8 MFMAs per K step (the 64x64 3x3 tile with one tap would
+//     give a wave 2).  The tile is TK x TC with TK, TC in {64, 128} and
+//     the block has TK*TC/2048 waves (8 / 4 / 2), so every wave of
+//     every tile shape has the same 8-fragment inner loop.  The host
+//     cuts K and C into 128s plus one 64 remainder (192 = 128 + 64) and
+//     launches one grid per tile shape present.
+//   - two LDS buffer sets, next chunk prefetched into registers before
+//     the MFMA phase (T14 above).  128x128: 2 * 256 rows * 320 B less
+//     the never-addressed pad of the last row = 163776 B, one block per
+//     CU; 128x64: 122880 B; 64x64: 81920 B.
+//   - split-K slabs ws[nsplit][K*C], reduced by k_wrw_reduce (n = K*C).
+//
+// Constraints: NHWC bf16, C % 64 == 0, K % 64 == 0, stride 1 (any H, W
+// >= 1) or stride 2 (H, W even), pad 0, dilation 1, groups 1.
+
+#define W1_CP 128
+
+// x row (in units of C) of flattened output pixel n0 * Ho*Wo + r, where
+// r may run past Ho*Wo by less than a chunk.
+__device__ __forceinline__ size_t w1_xrow(long n0, unsigned r, int H,
+                                          int W, unsigned Ho, unsigned Wo) {
+    const unsigned dn = r / (Ho * Wo);
+    r -= dn * (Ho * Wo);
+    const unsigned ho = r / Wo;
+    const unsigned wo = r - ho * Wo;
+    return ((size_t)(n0 + dn) * H + 2 * ho) * W + 2 * wo;
+}
+
+// Stage one operand of a chunk into registers: item i = t + it * NT is
+// pixel pair (i >> 3) & 63 x channels ((i >> 9) * 64 + (i & 7) * 8 ..+7).
+// S2: rows are x rows of a stride-2 conv; n0, r0 locate the chunk's
+// first pixel p0 (p0 = n0 * Ho*Wo + r0).
+template <int NT, int IT, bool S2>
+__device__ __forceinline__ void w1_issue(
+        const ushort_t* __restrict__ g, long p0, long M, int ld, int ch0,
+        int t, long n0, unsigned r0, int H, int W, int Ho, int Wo,
+        V16 (&v)[IT][2]) {
+    #pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int i = t + it * NT;
+        const int off = ((i >> 3) & 63) * 2;
+        const int ch = ch0 + (i >> 9) * 64 + (i & 7) * 8;
+        #pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            if (p0 + off + e < M) {
+                const size_t row = S2
+                    ? w1_xrow(n0, r0 + off + e, H, W, Ho, Wo)
+                    : (size_t)(p0 + off + e);
+                v[it][e].u4 = *reinterpret_cast<const u32x4*>(
+                    g + row * (size_t)ld + ch);
+            } else {
+                v[it][e].u4 = u32x4{0u, 0u, 0u, 0u};
+            }
+        }
+    }
+}
+
+template <int NT, int IT>
+__device__ __forceinline__ void w1_write(short* __restrict__ tile, int t,
+                                         const V16 (&v)[IT][2]) {
+    #pragma unroll
+    for (int it = 0; it < IT; ++it) {
+        const int i = t + it * NT;
+        const int p = ((i >> 3) & 63) * 2;
+        const int r8 = (i >> 9) * 64 + (i & 7) * 8;
+        #pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int row = r8 + j;
+            *reinterpret_cast<unsigned int*>(
+                &tile[row * DY_STRIDE + DSWZ(row, p)]) =
+                (unsigned int)(unsigned short)v[it][0].s[j]
+                | ((unsigned int)(unsigned short)v[it][1].s[j] << 16);
+        }
+    }
+}
+
+template <int TK, int TC>
+struct W1Regs {
+    static constexpr int NT = TK * TC / 32;   // 8 fragments per wave
+    static constexpr int IK = TK * 8 / NT;    // staging items per thread
+    static constexpr int IX = TC * 8 / NT;
+    V16 vdy[IK][2];
+    V16 vx[IX][2];
+};
+
+template <int TK, int TC>
+__device__ __forceinline__ void w1_issue_chunk(
+        const ushort_t* __restrict__ x, const ushort_t* __restrict__ dy,
+        long q, long M, int H, int W, int Ho, int Wo, int C, int K,
+        int stride, int kb, int cb, int t, W1Regs<TK, TC>& r) {
+    typedef W1Regs<TK, TC> R;
+    const long p0 = q * W1_CP;
+    w1_issue<R::NT, R::IK, false>(dy, p0, M, K, kb, t, 0, 0u, H, W, Ho,
+                                  Wo, r.vdy);
+    if (stride == 2) {
+        const long hw = (long)Ho * Wo;
+        const long n0 = p0 / hw;         // block-uniform, once per chunk
+        w1_issue<R::NT, R::IX, true>(x, p0, M, C, cb, t, n0,
+                                     (unsigned)(p0 - n0 * hw), H, W, Ho,
+                                     Wo, r.vx);
+    } else {
+        w1_issue<R::NT, R::IX, false>(x, p0, M, C, cb, t, 0, 0u, H, W, Ho,
+                                      Wo, r.vx);
+    }
+}
+
+template <int TK, int TC>
+__global__ __launch_bounds__(TK * TC / 32) void k_conv1x1_wrw(
+        const ushort_t* __restrict__ x, const ushort_t* __restrict__ dy,
+        float* __restrict__ ws, long M, int H, int W, int Ho, int Wo,
+        int C, int K, int stride, int k0, int c0, int nct, int nsplit) {
+    typedef W1Regs<TK, TC> R;
+    constexpr int BUF = (TK + TC) * DY_STRIDE;
+    // the pad columns (>= W1_CP) of the very last row are never addressed
+    __shared__ short lds[2 * BUF - (DY_STRIDE - W1_CP)];
+
+    const int tile = blockIdx.x / nsplit;
+    const int split = blockIdx.x % nsplit;
+    const int kb = k0 + (tile / nct) * TK;
+    const int cb = c0 + (tile % nct) * TC;
+
+    const int t = threadIdx.x;
+    const int lane = t & 63;
+    const int wid = t >> 6;
+    const int wk = wid / (TC / 64);      // 32-row k band of the tile
+    const int wc = wid % (TC / 64);      // 64-column c band
+    const int row16 = lane & 15;
+    const int slot8 = (lane >> 4) * 8;
+
+    f32x4 acc[2][4];
+    #pragma unroll
+    for (int mf = 0; mf < 2; ++mf)
+        #pragma unroll
+        for (int nf = 0; nf < 4; ++nf)
+            #pragma unroll
+            for (int r = 0; r < 4; ++r)
+                acc[mf][nf][r] = 0.f;
+
+    const long chunks_total = (M + W1_CP - 1) / W1_CP;
+
+    R regs;
+    // Prologue: stage chunk 0 into buffer 0, issue chunk 1's loads.
+    if (split < chunks_total) {
+        w1_issue_chunk<TK, TC>(x, dy, split, M, H, W, Ho, Wo, C, K, stride,
+                               kb, cb, t, regs);
+        w1_write<R::NT, R::IK>(lds, t, regs.vdy);
+        w1_write<R::NT, R::IX>(lds + TK * DY_STRIDE, t, regs.vx);
+    }
+    __syncthreads();
+    if (split + nsplit < chunks_total)
+        w1_issue_chunk<TK, TC>(x, dy, split + nsplit, M, H, W, Ho, Wo, C,
+                               K, stride, kb, cb, t, regs);
+
+    int cur = 0;
+    for (long q = split; q < chunks_total; q += nsplit, cur ^= 1) {
+        const short* dy_t = lds + cur * BUF;
+        const short* x_t = dy_t + TK * DY_STRIDE;
+
+        // ---- MFMA phase (chunk q, buffer cur) ----
+        #pragma unroll
+        for (int kc = 0; kc < W1_CP / 32; ++kc) {
+            bf16x8 afrag[2], bfrag[4];
+            #pragma unroll
+            for (int mf = 0; mf < 2; ++mf) {
+                const int row = wk * 32 + mf * 16 + row16;
+                afrag[mf] = *reinterpret_cast<const bf16x8*>(
+                    &dy_t[row * DY_STRIDE + DSWZ(row, kc * 32 + slot8)]);
+            }
+            #pragma unroll
+            for (int nf = 0; nf < 4; ++nf) {
+                const int row = wc * 64 + nf * 16 + row16;
+                bfrag[nf] = *reinterpret_cast<const bf16x8*>(
+                    &x_t[row * DY_STRIDE + DSWZ(row, kc * 32 + slot8)]);
+            }
+            #pragma unroll
+            for (int mf = 0; mf < 2; ++mf)
+                #pragma unroll
+                for (int nf = 0; nf < 4; ++nf)
+                    acc[mf][nf] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        afrag[mf], bfrag[nf], acc[mf][nf], 0, 0, 0);
+        }
+
+        // ---- stage chunk q+1 into the other buffer; issue q+2 ----
+        if (q + nsplit < chunks_total) {
+            short* ndy = lds + (cur ^ 1) * BUF;
+            w1_write<R::NT, R::IK>(ndy, t, regs.vdy);
+            w1_write<R::NT, R::IX>(ndy + TK * DY_STRIDE, t, regs.vx);
+            if (q + 2 * nsplit < chunks_total)
+                w1_issue_chunk<TK, TC>(x, dy, q + 2 * nsplit, M, H, W, Ho,
+                                       Wo, C, K, stride, kb, cb, t, regs);
+        }
+        __syncthreads();
+    }
+
+    float* slab = ws + (size_t)split * K * C;
+    #pragma unroll
+    for (int mf = 0; mf < 2; ++mf)
+        #pragma unroll
+        for (int nf = 0; nf < 4; ++nf)
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = kb + wk * 32 + mf * 16 + (lane >> 4) * 4 + r;
+                const int c = cb + wc * 64 + nf * 16 + (lane & 15);
+                slab[(size_t)k * C + c] = acc[mf][nf][r];
+            }
+}
+
+// K and C are cut into 128s plus one 64 remainder.
+static int w1_tiles(int C, int K) {
+    return ((K + 127) / 128) * ((C + 127) / 128);
+}
+
+extern "C" int conv1x1_wrw_supported(int H, int W, int C, int K,
+                                     int stride) {
+    if (C < 64 || K < 64 || C % 64 || K % 64 || H < 1 || W < 1) return 0;
+    if (stride == 1) return 1;
+    return stride == 2 && H % 2 == 0 && W % 2 == 0;
+}
+
+extern "C" int conv1x1_wrw_nsplit(int N, int Ho, int Wo, int C, int K) {
+    const long chunks = ((long)N * Ho * Wo + W1_CP - 1) / W1_CP;
+    long target = 256 / w1_tiles(C, K);   // one residency round
+    if (target < 1) target = 1;
+    if (target > chunks) target = chunks;
+    return (int)target;
+}
+
+// One grid over the nkt x nct tiles of shape TK x TC that start at
+// channel (k0, c0).
+template <int TK, int TC>
+static void w1_launch(const ushort_t* x, const ushort_t* dy, float* ws,
+                      long M, int H, int W, int Ho, int Wo, int C, int K,
+                      int stride, int k0, int nkt, int c0, int nct,
+                      int nsplit, hipStream_t s) {
+    if (nkt == 0 || nct == 0) return;
+    hipLaunchKernelGGL((k_conv1x1_wrw<TK, TC>), dim3(nkt * nct * nsplit),
+                       dim3(TK * TC / 32), 0, s, x, dy, ws, M, H, W, Ho,
+                       Wo, C, K, stride, k0, c0, nct, nsplit);
+}
+
+extern "C" void launch_conv1x1_wrw(
+        const ushort_t* x, const ushort_t* dy, float* ws, float* dw,
+        int N, int H, int W, int C, int K, int stride, int accum,
+        hipStream_t s) {
+    const int Ho = stride == 2 ? H / 2 : H;
+    const int Wo = stride == 2 ? W / 2 : W;
+    const long M = (long)N * Ho * Wo;
+    const int nsplit = conv1x1_wrw_nsplit(N, Ho, Wo, C, K);
+    const int k128 = K / 128, c128 = C / 128;
+    const int k64 = (K % 128) / 64, c64 = (C % 128) / 64;
+    w1_launch<128, 128>(x, dy, ws, M, H, W, Ho, Wo, C, K, stride, 0, k128,
+                        0, c128, nsplit, s);
+    w1_launch<128, 64>(x, dy, ws, M, H, W, Ho, Wo, C, K, stride, 0, k128,
+                       c128 * 128, c64, nsplit, s);
+    w1_launch<64, 128>(x, dy, ws, M, H, W, Ho, Wo, C, K, stride,
+                       k128 * 128, k64, 0, c128, nsplit, s);
+    w1_launch<64, 64>(x, dy, ws, M, H, W, Ho, Wo, C, K, stride,
+                      k128 * 128, k64, c128 * 128, c64, nsplit, s);
+    launch_wrw_reduce(ws, dw, (long)K * C, nsplit, accum, s);
 }
 
 // =====================================================================
@@ -2354,15 +2642,7 @@ extern "C" void launch_conv3x3_s2_wrw(
     hipLaunchKernelGGL(k_conv3x3_s2_wrw, dim3(tiles * nsplit), dim3(512),
                        lds_bytes, s, x, dy, ws, N, Ho, Wo, C, K, XT2S,
                        nsplit);
-    const long n = (long)K * 9 * C;
-    const int ngroups = (nsplit + 15) / 16;
-    const long nchunks = (n + 1023) / 1024;
-    if (ngroups > 1)
-        hipMemsetAsync(dw, 0, n * sizeof(float), s);
-    long blocks = nchunks * ngroups;
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(k_wrw_reduce, dim3((unsigned)blocks), dim3(256), 0,
-                       s, ws, dw, n, nsplit, ngroups, nchunks, 0);
+    launch_wrw_reduce(ws, dw, (long)K * 9 * C, nsplit, 0, s);
 }
 
 // =====================================================================

@@ -101,6 +101,13 @@ int conv3x3_wrw_nsplit(int N, int H, int W, int C, int K);
 void launch_conv3x3_wrw(const unsigned short* x, const unsigned short* dy,
                         float* ws, float* dw, int N, int H, int W, int C,
                         int K, int accum, hipStream_t s);
+// 1x1 weight gradient, pad 0, stride 1 or 2; x is (N,H,W,C), dy is
+// (N,Ho,Wo,K), ws holds nsplit slabs of K*C floats, dw K*C floats.
+int conv1x1_wrw_supported(int H, int W, int C, int K, int stride);
+int conv1x1_wrw_nsplit(int N, int Ho, int Wo, int C, int K);
+void launch_conv1x1_wrw(const unsigned short* x, const unsigned short* dy,
+                        float* ws, float* dw, int N, int H, int W, int C,
+                        int K, int stride, int accum, hipStream_t s);
 int conv3x3_mm_supported(int H, int W, int C, int K);
 void launch_conv3x3_mm(const unsigned short* x, const unsigned short* w,
                        unsigned short* y, int N, int H, int W, int C,

@@ -288,6 +288,48 @@ class _FusedConvFunction(torch.autograd.Function):
         return dx, dw, None, None, None, None, None, None
 
 
+class _FusedConv1x1Function(torch.autograd.Function):
+    """1x1 conv (stride 1 or 2, pad 0) with the weight gradient computed
+    by k_conv1x1_wrw: fp32, written or added straight into the gradient
+    sink.  Forward and grad_input stay on the library.
+    """
+
+    @staticmethod
+    def forward(ctx, x, weight, wb, stride, sink=None):
+        ctx.conv_sink = sink
+        ctx.conv_param = weight if sink is not None else None
+        ctx.save_for_backward(x, wb)
+        ctx.conv_stride = stride
+        return torch.nn.functional.conv2d(x, wb, None, stride)
+
+    @staticmethod
+    def backward(ctx, dy):
+        ext = ops._load_extension()
+        x, wb = ctx.saved_tensors
+        stride = ctx.conv_stride
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.ops.aten.convolution_backward(
+                dy, x, wb, None, stride, [0, 0], [1, 1], False, [0, 0], 1,
+                [True, False, False])[0]
+        if ctx.conv_sink is None and not ctx.needs_input_grad[1]:
+            return dx, None, None, None, None
+        n, k, ho, wo = dy.shape
+        c = x.shape[1]
+        nsplit = ext.conv1x1_wrw_nsplit(n, ho, wo, c, k)
+        ws = torch.empty(nsplit * k * c, dtype=torch.float32,
+                         device=x.device)
+        if ctx.conv_sink is not None:
+            from adaptdl_amd.torch import _engine
+            ext.conv1x1_wrw(x, dy, ws, ctx.conv_sink, stride[0], True)
+            _engine.grad_written(ctx.conv_param)
+            return dx, None, None, None, None
+        dw = torch.empty(k, c, 1, 1, dtype=torch.float32, device=x.device)
+        ext.conv1x1_wrw(x, dy, ws, dw, stride[0])
+        return dx, dw, None, None, None
+
+
 class _S2ConvFunction(torch.autograd.Function):
     """3x3 stride-2 conv with backward-data on the polyphase MFMA kernel.
 
@@ -392,10 +434,12 @@ class _S2Conv1x1Function(torch.autograd.Function):
 
 
 _WRW_W4_DEFAULT = "1"   # set by measurement, see FusedConv2d._wrw_ok
+_WRW_1X1_DEFAULT = "1"  # set by measurement, see FusedConv2d._wrw1x1_ok
 
 
 class FusedConv2d(nn.Conv2d):
-    """Conv2d whose 3x3/s1 weight gradient runs the MFMA wrw kernel."""
+    """Conv2d whose 3x3/s1 and 1x1 (s1, s2) weight gradients run the
+    MFMA wrw kernels."""
 
     def _wrw_ok(self, x):
         if not (x.is_cuda and x.dtype == torch.bfloat16 and
@@ -415,6 +459,27 @@ class FusedConv2d(nn.Conv2d):
                 os.getenv("ADAPTDL_WRW_W4", _WRW_W4_DEFAULT) != "1":
             return False
         return bool(ext.conv_wrw_ok(n, h, w, c, self.out_channels))
+
+    def _wrw1x1_ok(self, x):
+        # 1x1 stride-1/2 weight gradient on k_conv1x1_wrw (fp32, added
+        # straight into the gradient sink).  ADAPTDL_WRW_1X1=1/0 forces
+        # it on/off.  Default on: ahead of MIOpen on all eight measured
+        # shapes in both runs (35 vs 42, 29 vs 75, 29 vs 68 us on the
+        # flagship shortcuts) and 40.0 vs 40.4 ms/step in context
+        # (profiles/wrw_1x1_time.json).
+        if os.getenv("ADAPTDL_WRW_1X1", _WRW_1X1_DEFAULT) != "1":
+            return False
+        if not (x.is_cuda and x.dtype == torch.bfloat16 and
+                x.dim() == 4 and ops.has_extension() and
+                self.bias is None and self.groups == 1 and
+                self.kernel_size == (1, 1) and
+                self.stride in ((1, 1), (2, 2)) and
+                self.padding == (0, 0) and self.dilation == (1, 1) and
+                x.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        n, c, h, w = x.shape
+        return bool(ops._load_extension().conv1x1_wrw_ok(
+            h, w, c, self.out_channels, self.stride[0]))
 
     def _s2_ok(self, x):
         if os.getenv("ADAPTDL_S2_BWD") == "0":   # A/B escape hatch
@@ -495,6 +560,15 @@ class FusedConv2d(nn.Conv2d):
                                             self.stride, self.padding,
                                             self.dilation, self.groups,
                                             sink)
+        if not self._s2_1x1_ok(x) and self._wrw1x1_ok(x) and \
+                (self.weight.requires_grad or x.requires_grad):
+            sink = None
+            if self.weight.requires_grad and torch.is_grad_enabled() \
+                    and self.weight.is_contiguous():
+                sink = _engine.grad_sink(self.weight)
+            return _FusedConv1x1Function.apply(x, self.weight,
+                                               self._cast_weight(),
+                                               self.stride, sink)
         # The remaining convs take the library's weight gradient (bf16
         # under autocast).  With a gradient sink they get the cached
         # bf16 weight, which autocast would otherwise re-cast on every
